@@ -2,6 +2,7 @@
 """Benchmark of the multigrid inner loop on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload marine128|triaxial256|...]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one multigrid cycle (pre-smoothing, residual, restriction, recursion,
 prolongation, post-smoothing, residual norm) of BASELINE.json's configuration on one
@@ -11,17 +12,27 @@ headline metric is BASELINE.json's: Mcells*smoother-iterations per second, i.e.
     work = sum over all smoother calls of the cycle of  nu * n_cells(level) [* directions]
 
 divided by wall time, aggregated over all GPUs of the job (one independent source per
-GPU: weak scaling). Rank 0 prints ONE JSON line, which also carries
+GPU: weak scaling). Rank 0 prints ONE JSON line with `ms_per_step`
+(wall time of one timed cycle), which also carries
 
 * "roofline": algorithmic HBM bytes of the dominant kernel PER LAUNCH (a level-0 line smoother
   colour pass; 200 B per cell-sweep tri-axial) over its measured duration
-  (HIP events on the launch stream, inside the timed region), against the 8 TB/s HBM peak;
-  "roofline.north_star_kernel": the same for core.gauss_seidel (k_gs_point_tile) at 256^3;
-* "smoothers_256" (1 GPU): the four smoothers on a 256^3 tri-axial level -- the kernel figure
+  (HIP events on the launch stream, inside the timed region), against the 8 TB/s HBM peak.
+
+A plain run sets up, warms up, times the K cycles and prints that line. With --full (1 GPU) it
+goes on to measure, in runs of their own after the timed cycles:
+
+* "roofline.north_star_kernel": the same figure for core.gauss_seidel (k_gs_point_tile) at 256^3;
+* "smoothers_256": the four smoothers on a 256^3 tri-axial level -- the kernel figure
   BASELINE.json's target (>= 40 % of the HBM roofline on gauss_seidel at 256^3) is stated for;
+* "time_to_tol", "fp64_storage", "survey_8_sources", "survey_config5" (see their functions);
 * "cpu_baseline": the oracle (C restatement of the reference's sequential numba kernels,
   oracle/) timed on this host: one thread on a bounded sample of the same workload, and all
   cores in throughput mode (one job per core), CPU model and core count stated.
+
+--dump-outputs DIR: after the timed cycles, rank 0 writes the field they computed as .npy files
+into DIR (dump_outputs); the workloads are deterministic, so runs with the same arguments start
+from the same inputs and two builds can be compared output for output.
 
 The default workload is BASELINE.json config 3 (256^3 tri-axial, W-cycle + semicoarsening + line
 relaxation), the largest single-GPU configuration.
@@ -540,6 +551,27 @@ def pmc_traffic(workload_name, kernel):
     return None, None
 
 
+DUMP_SAMPLE = 1 << 21          # edges of the field --dump-outputs writes at most (2 x 16 MB of float64)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(path, b):
+    """The output of the timed path: the finest-level field after the last timed cycle (what a caller
+    of solver.multigrid receives in its `efield`), as float64 `efield_real.npy` / `efield_imag.npy`
+    in DIR -- every edge of a grid with at most DUMP_SAMPLE of them, else a fixed sample of
+    DUMP_SAMPLE edges (seed DUMP_SEED) in increasing edge order."""
+    import torch
+    e = b.hier.top.solution()
+    n = e.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        e = e[torch.from_numpy(idx).to(e.device)]
+    e = e.cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'efield_real.npy'), np.ascontiguousarray(e.real, dtype=np.float64))
+    np.save(os.path.join(path, 'efield_imag.npy'), np.ascontiguousarray(np.imag(e), dtype=np.float64))
+
+
 def run_gpu(args):
     import torch
     import torch.distributed as dist
@@ -617,6 +649,8 @@ def run_gpu(args):
         dt_max, dt_min, work_all = tmax[0].item(), tmin_[0].item(), tsum[1].item()
     else:
         dt_max, dt_min, work_all = dt, dt, float(work)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, b)
 
     out = None
     if rank == 0:
@@ -680,19 +714,20 @@ def run_gpu(args):
                     'GB/s': bytes_per_launch / (v['ms'] / v['launches'] * 1e-3) / 1e9}
                     for k, v in stats.items()}},
         }
-    if rank == 0 and world == 1 and not args.no_ttt:
+    full = rank == 0 and world == 1 and args.full      # the measurements beyond the headline (--full)
+    if full and not args.no_ttt:
         try:
             out['time_to_tol'] = time_to_tol(args.workload, wl, b)
         except Exception as exc:        # informational block: never takes the bench line down
             out['time_to_tol'] = {'error': repr(exc)}
-    if rank == 0 and world == 1 and not args.no_ttt and b.hier.line_compact:
+    if full and not args.no_ttt and b.hier.line_compact:
         try:       # both storages in one line (the review of round 5): the cycle with fp64 records, same process, same box
             out['fp64_storage'] = fs = cycle_fp64_storage(wl, model, device, max(2, min(args.steps, 10)))
             out['roofline']['frac_fp64_storage'] = fs['frac']
             out['ms_per_step_fp64_storage'] = fs['ms_per_step']
         except Exception as exc:        # informational block: never takes the bench line down
             out['fp64_storage'] = {'error': repr(exc)}
-    if rank == 0 and world == 1 and not args.no_256:
+    if full and not args.no_256:
         del b            # (its buffers stay with the caching allocator: handing tens of GB back to the driver makes a later
                          #  hipMalloc take 1.7 - 2 s on this stack, profiles/r05_config5_stall.txt)
         out['smoothers_256'] = sm = smoothers_256(device)
@@ -719,12 +754,12 @@ def run_gpu(args):
         for lab, v in sm['smoothers'].items():
             if lab.startswith('gauss_seidel_'):
                 out['roofline'][f"line_{lab[13]}_256_frac{'_compact' if lab.endswith('compact records') else '_fp64'}"] = v['frac']
-    if rank == 0 and world == 1 and not args.no_survey:
+    if full and not args.no_survey:
         try:
             out['survey_8_sources'] = survey_8(device)
         except Exception as exc:        # informational block: never takes the bench line down
             out['survey_8_sources'] = {'error': repr(exc)}
-    if rank == 0 and world == 1 and not args.no_survey:
+    if full and not args.no_survey:
         try:
             out['survey_config5'] = survey_config5(device)
         except Exception as exc:        # informational block: never takes the bench line down
@@ -915,6 +950,11 @@ def main():
     ap.add_argument('--workload', default='triaxial256',
                     help="default: BASELINE.json config 3 (256^3 tri-axial, W-cycle + sc + lr), the largest "
                          "single-GPU configuration, the size the metric's 40 %% target is stated at")
+    ap.add_argument('--full', action='store_true',
+                    help="after the headline, the measurements of their own (1 GPU): 'time_to_tol', 'fp64_storage', "
+                         "'smoothers_256', the survey blocks and 'cpu_baseline' (each can be left out by its --no-* flag)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the field the timed cycles computed to DIR/*.npy (float64; dump_outputs)")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--opt', action='append', default=[],
                     help='library tuning option name=value (emg3d_set_option), for experiments')
@@ -927,6 +967,8 @@ def main():
     ap.add_argument('--line-factors', default=None, choices=['resident', 'rebuild', 'single'],
                     help="factor-memory policy of the hierarchy (solver.Hierarchy; default: resident)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")       # (fixed_cycles = 0 would mean: cycle until converged)
     if args.line_factors:
         os.environ['EMG3D_AMD_LINE_FACTORS'] = args.line_factors
     if 'RANK' not in os.environ and args.gpus > 1:
@@ -944,7 +986,7 @@ def main():
         return
     out, wl, rank, world = run_gpu(args)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = run_cpu_baseline(wl)
             if 'reduced_copy' in out.get('time_to_tol', {}):
                 time_to_tol_cpu(out['time_to_tol'], out['value'])

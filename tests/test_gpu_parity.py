@@ -2381,6 +2381,39 @@ def test_bench_two_ranks_through_its_own_launcher(backend):
     assert out['value'] == pytest.approx(2 * out['config']['cell_sweeps_per_step'] * 3 / (out['ms_per_step'] * 3e-3) / 1e6, rel=0.02)
 
 
+def test_bench_plain_run_dumps_the_field_of_its_timed_cycles(tmp_path):
+    """`python bench.py --steps K --dump-outputs DIR` without --full: K timed cycles, `ms_per_step`, none of the
+    blocks of --full, and the field after the last timed cycle in DIR -- the same field a solver.multigrid call
+    with as many cycles from the same start leaves (the bench's preparation + warm-up + timed cycles)."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'triaxial64', '--steps', '3',
+                        '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0 and out['value'] > 0
+    assert out['value'] == pytest.approx(out['config']['cell_sweeps_per_step'] / (out['ms_per_step'] * 1e-3) / 1e6, rel=1e-9)
+    assert out['cpu_baseline'] is None
+    assert not {'time_to_tol', 'fp64_storage', 'smoothers_256', 'survey_8_sources', 'survey_config5'} & set(out)
+    re_, im_ = np.load(tmp_path / 'efield_real.npy'), np.load(tmp_path / 'efield_imag.npy')
+    assert re_.dtype == im_.dtype == np.float64
+    # the same cycles in this process: the bench's hierarchy and cycle driver, as many cycles as the bench ran
+    wl = bench.workload('triaxial64')
+    grid = emg3d.TensorMesh(wl['h'], wl['origin'])
+    b = bench.Bench(wl, emg3d.Model(grid, **wl['res']), torch.device('cuda', 0))
+    b.cycles((b.solver._GRAPH_AFTER + 1) * b.var.maxcycle)
+    b.cycles(1)
+    b.cycles(3)
+    e = b.hier.top.solution().cpu().numpy()
+    assert re_.size == grid.n_edges <= bench.DUMP_SAMPLE
+    assert relerr(re_ + 1j * im_, e) < 1e-12
+
+
 @pytest.mark.slow
 @pytest.mark.parametrize('wlname', ['marine128', 'salt384'])
 def test_bench_eight_ranks_dry_run_on_one_gpu(wlname):

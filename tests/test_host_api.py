@@ -482,6 +482,37 @@ def test_bench_helpers_without_a_gpu():
     assert bench.pmc_traffic('no_such_workload', 'k') == (None, None)
 
 
+def test_bench_dump_outputs_and_arguments_without_a_gpu(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the field of the timed cycles as float64 real / imaginary parts, the whole
+    field of a small grid, a fixed sample of a large one (the same edges in every run); --steps 0 is refused
+    (it would cycle until converged)."""
+    import subprocess
+    import sys
+    import types
+    import torch
+    import bench
+
+    def fake_bench(field):
+        return types.SimpleNamespace(hier=types.SimpleNamespace(top=types.SimpleNamespace(solution=lambda: field)))
+    rng = np.random.default_rng(3)
+    e = rng.standard_normal(5000) + 1j * rng.standard_normal(5000)
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 8000)
+    bench.dump_outputs(str(tmp_path / 'whole'), fake_bench(torch.from_numpy(e)))
+    re_, im_ = np.load(tmp_path / 'whole' / 'efield_real.npy'), np.load(tmp_path / 'whole' / 'efield_imag.npy')
+    assert re_.dtype == im_.dtype == np.float64 and np.array_equal(re_ + 1j * im_, e)
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 1000)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), fake_bench(torch.from_numpy(e)))
+    a = np.load(tmp_path / 'a' / 'efield_real.npy') + 1j * np.load(tmp_path / 'a' / 'efield_imag.npy')
+    b = np.load(tmp_path / 'b' / 'efield_real.npy') + 1j * np.load(tmp_path / 'b' / 'efield_imag.npy')
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(e.size, 1000, replace=False))
+    assert a.size == 1000 and np.array_equal(a, b) and np.array_equal(a, e[idx])
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '0'],
+                       capture_output=True, text=True, timeout=120, cwd=root)
+    assert r.returncode == 2 and '--steps must be at least 1' in r.stderr
+
+
 def test_model_drops_a_device_snapshot_when_a_property_is_replaced():
     """parallel.broadcast_model leaves HBM copies of the property arrays on the model it RETURNS
     (`_device_props`); replacing a property array must drop that array's copy."""

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
-B="python $R/bench.py --workload $WL --no-256 --no-survey --no-cpu-baseline"
+B="python $R/bench.py --full --workload $WL --no-256 --no-survey --no-cpu-baseline"
 timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace -o run -- $B > $O/trace.log 2>&1
 python $R/tools/rocpd_summary.py $O/trace/run_results.db > $R/gpurun_out/${TAG}_${WL}_kernel_stats.txt
 python $R/tools/trace_by_grid.py $O/trace/run_results.db k_line_ > $R/gpurun_out/${TAG}_${WL}_line_launches_by_level.txt
