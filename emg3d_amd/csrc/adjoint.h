@@ -88,6 +88,87 @@ int emg3d_dev_gradient_accumulate(int nx, int ny, int nz, int is_complex, const 
 
 }  // extern "C"
 
+// ---- sensitivity products (Simulation.jvec, emg3d/simulations.py:1352-1362): the transpose of the
+// kernel above. A model perturbation v (cells, per component) becomes a source field on the edges,
+//     g = -s mu0 * e * 1/4 * sum over the cells that share the edge of (volume * v)
+// (the reference takes the operator from discretize's get_edge_inner_product_deriv). ONE gather
+// kernel over the nodes' index space: thread (ix, iy, iz), ix = 0..nx, iy = 0..ny, iz = 0..nz, owns
+// the x-, y- and z-edge that start at its node; the up to four cells of an edge are added in the
+// order k_gradient_accumulate reaches the same cell / edge pairs (z outer, y, x inner), so the result
+// does not depend on the launch shape. Written, not accumulated. Edges on the PEC boundary carry
+// e = 0 and hence g = 0: no special case.
+namespace {
+
+__device__ __forceinline__ cplx sens_edge(cplx nsmu0, cplx e, double q) { return (nsmu0 * e) * q; }
+__device__ __forceinline__ double sens_edge(double nsmu0, double e, double q) { return (nsmu0 * e) * q; }
+
+template <class T>
+__global__ __launch_bounds__(256) void k_sensitivity_source(int nx, int ny, int nz, const T *ex, const T *ey, const T *ez,
+                                                            T nsmu0, const double *vol, const double *vx, const double *vy,
+                                                            const double *vz, T *gx, T *gy, T *gz)
+{
+    const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y, iz = blockIdx.z;
+    if (ix > nx || iy > ny || iz > nz) return;
+    // cell (i, j, k) exists? -- the lower neighbours of the node are (ix-1, iy-1, iz-1)
+    const bool x0 = ix > 0, x1 = ix < nx, y0 = iy > 0, y1 = iy < ny, z0 = iz > 0, z1 = iz < nz;
+#define CELL(i, j, k) ((size_t)(i) + (size_t)nx * ((j) + (size_t)ny * (k)))
+#define ADD(V, ok, i, j, k) if (ok) { const size_t c = CELL(i, j, k); a += vol[c] * V[c]; }
+    if (x1) {   // x-edge (ix; iy; iz): cells (ix, iy-1 | iy, iz-1 | iz)
+        double a = 0.0;
+        ADD(vx, y0 && z0, ix, iy - 1, iz - 1)
+        ADD(vx, y1 && z0, ix, iy, iz - 1)
+        ADD(vx, y0 && z1, ix, iy - 1, iz)
+        ADD(vx, y1 && z1, ix, iy, iz)
+        const size_t i = (size_t)ix + (size_t)nx * (iy + (size_t)(ny + 1) * iz);
+        gx[i] = sens_edge(nsmu0, ex[i], a / 4);
+    }
+    if (y1) {   // y-edge: cells (ix-1 | ix, iy, iz-1 | iz)
+        double a = 0.0;
+        ADD(vy, x0 && z0, ix - 1, iy, iz - 1)
+        ADD(vy, x1 && z0, ix, iy, iz - 1)
+        ADD(vy, x0 && z1, ix - 1, iy, iz)
+        ADD(vy, x1 && z1, ix, iy, iz)
+        const size_t i = (size_t)ix + (size_t)(nx + 1) * (iy + (size_t)ny * iz);
+        gy[i] = sens_edge(nsmu0, ey[i], a / 4);
+    }
+    if (z1) {   // z-edge: cells (ix-1 | ix, iy-1 | iy, iz)
+        double a = 0.0;
+        ADD(vz, x0 && y0, ix - 1, iy - 1, iz)
+        ADD(vz, x1 && y0, ix, iy - 1, iz)
+        ADD(vz, x0 && y1, ix - 1, iy, iz)
+        ADD(vz, x1 && y1, ix, iy, iz)
+        const size_t i = (size_t)ix + (size_t)(nx + 1) * (iy + (size_t)(ny + 1) * iz);
+        gz[i] = sens_edge(nsmu0, ez[i], a / 4);
+    }
+#undef CELL
+#undef ADD
+}
+
+}  // namespace
+
+extern "C" {
+
+int emg3d_dev_sensitivity_source(int nx, int ny, int nz, int is_complex, const void *ex, const void *ey, const void *ez,
+                                 double smu0_re, double smu0_im, const double *volumes, const double *vx, const double *vy,
+                                 const double *vz, void *gx, void *gy, void *gz, void *stream)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || !ex || !ey || !ez || !volumes || !vx || !vy || !vz || !gx || !gy || !gz)
+        return fail(EMG3D_ERR_BADARG, "sensitivity_source: bad argument");
+    const dim3 block(64, 4, 1), grid(cdiv(nx + 1, 64), cdiv(ny + 1, 4), nz + 1);
+    if (is_complex)
+        hipLaunchKernelGGL(k_sensitivity_source<cplx>, grid, block, 0, (hipStream_t)stream, nx, ny, nz, (const cplx *)ex,
+                           (const cplx *)ey, (const cplx *)ez, cplx(-smu0_re, -smu0_im), volumes, vx, vy, vz, (cplx *)gx,
+                           (cplx *)gy, (cplx *)gz);
+    else
+        hipLaunchKernelGGL(k_sensitivity_source<double>, grid, block, 0, (hipStream_t)stream, nx, ny, nz, (const double *)ex,
+                           (const double *)ey, (const double *)ez, -smu0_re, volumes, vx, vy, vz, (double *)gx, (double *)gy,
+                           (double *)gz);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
+
 // ---- before a solve: the source vector of a dipole or wire on the
 // device. The reference (fields._dipole_vector, emg3d/fields.py:792-938) walks, per straight
 // segment, over the cells of its bounding box and clips the segment against each cell; here one

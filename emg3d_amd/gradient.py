@@ -28,6 +28,22 @@ Magnetic point receivers (``magnetic=``): responses = ``get_magnetic_field`` int
 point, adjoint source = the transpose of exactly that map (``fields.get_magnetic_point_source_field``;
 the reference builds its ``_point_vector_magnetic`` from discretize's operators, emg3d/fields.py:749-789).
 
+Sensitivity products (``Sensitivity``, ``jvec``, ``jtvec``; reference ``Simulation.jvec`` / ``jtvec``,
+emg3d/simulations.py:1271-1434): a Gauss-Newton step multiplies the sensitivity matrix J (derivative of the
+complex responses with respect to the model properties) and its adjoint with vectors many times at ONE model.
+``Sensitivity`` is that linearisation point: it computes the forward fields once and keeps them per pair (in
+HBM, in pinned host memory, or not at all), and then
+
+    jvec(v)  = P A^-1 G v       G v: cells -> edges, times the forward field, times -s mu0
+                                (emg3d_dev_sensitivity_source, written into the hierarchy's source vector);
+                                one solve per pair at ``tol_gradient``; P: the receivers' linear interpolation
+    jtvec(y) = G^H A^-H P^H y   steps 4-8 above with ``residual w`` replaced by ``y`` and the KEPT forward
+                                field in step 6 (emg3d_dev_gradient_accumulate is the transpose of G)
+
+Convention: ``jtvec`` returns the real array with ``sum(v * jtvec(y)) == Re sum_i conj(y_i) jvec(v)_i`` for
+every real ``v`` -- which makes ``misfit_and_gradient == jtvec(residual * weights)`` the gradient of
+``sum w |r|^2 / 2``.
+
 Limits as in the reference: no epsilon_r / mu_r.
 """
 import numpy as np
@@ -35,7 +51,7 @@ import numpy as np
 from emg3d_amd import fields, models
 from emg3d_amd.fields import Field
 
-__all__ = ['misfit_and_gradient', 'residual_source_field']
+__all__ = ['misfit_and_gradient', 'residual_source_field', 'Sensitivity', 'jvec', 'jtvec', 'expand_vector']
 
 _DCHAIN = {          # d sigma / d property, applied to the gradient w.r.t. conductivity (emg3d/maps.py:120-330)
     'Conductivity': lambda g, p: g,
@@ -97,101 +113,55 @@ def misfit_and_gradient(model, sources, frequencies, receivers, observed, weight
     ``{'log': False}`` with a conductivity model).
     With an initialised process group the pairs are sharded over the ranks and both results are
     all-reduced: every rank returns the complete misfit and gradient."""
-    import torch
-    from emg3d_amd import _lib, parallel, solver
-    from emg3d_amd._device import _ptr, _stream
+    from emg3d_amd import _lib
     _lib.require_gpu()
+    lin = Sensitivity(model, sources, frequencies, receivers, solver_opts=solver_opts, tol_gradient=tol_gradient,
+                      costs=costs, grids=grids, interpolate_opts=interpolate_opts, magnetic=magnetic, keep=False)
+    lin._order = list(lin._mine)          # pair by pair in the order of the shard, as ever
+    try:
+        misfit, grad = lin.misfit_and_gradient(observed, weights)
+        return misfit, grad, lin.info
+    finally:
+        lin.release()
+
+
+def _check_model(model):
     for name, prop in (('el. permittivity', model.epsilon_r), ('magn. permeability', model.mu_r)):
         if prop is not None and not np.allclose(prop, 1.0):
             raise NotImplementedError(f"Gradient not implemented for {name}.")
-    mgrid = model.grid
-    opts = dict(solver_opts or {})
-    opts.setdefault('sslsolver', True)
-    rec = _receiver_tuple(receivers)
-    mag = np.zeros(len(rec[0]), dtype=bool) if magnetic is None else np.asarray(magnetic, dtype=bool)
-    pairs = parallel.srcfreq_pairs(sources, frequencies)
-    rank, world = parallel.rank_and_world()
-    mine = parallel.shard(len(pairs), rank, world, costs)
-    dev = torch.device('cuda', torch.cuda.current_device())
-    ncell = mgrid.n_cells
-    grad = torch.zeros(3 * ncell, dtype=torch.float64, device=dev)
-    misfit = 0.0
-    hierarchies = {}
-    on_grid = {}                 # per computational grid: (grid, model on it, cell volumes, averaging plan)
-    info = {}
 
-    def computational(pair):
-        g = grids.get(pair) if isinstance(grids, dict) else grids
-        if g is None or g == mgrid:
-            g = mgrid
-        key = id(g) if g is not mgrid else 0
-        if key not in on_grid:
-            vol = torch.from_numpy(np.ascontiguousarray(g.cell_volumes, dtype=np.float64)).to(dev)
-            plan = None if g is mgrid else models._VolumeAverage(mgrid, g)
-            on_grid[key] = (g, model.interpolate_to_grid(g, **(interpolate_opts or {})), vol, plan)
-        return (key,) + on_grid[key]
 
-    for i in mine:
-        sname, fname = pairs[i]
-        freq = frequencies[fname]
-        gkey, grid, gmodel, vol, plan = computational((sname, fname))
-        nx, ny, nz = grid.shape_cells
-        sfield = fields.get_source_field(grid, sources[sname], freq)
-        hkey = (complex(sfield.sval), gkey)
-        hier = hierarchies.get(hkey)
-        if hier is None:
-            hierarchies.clear()                       # one (frequency, grid) at a time in HBM
-            hier = hierarchies[hkey] = solver.Hierarchy(models.VolumeModel(gmodel, sfield))
-        top = hier.top
-        _, finfo = solver.solve(gmodel, sfield, return_info=True, always_return=True, hierarchy=hier, _download=False,
-                                _sparse_source=True, **opts)
-        e_fwd = torch.empty_like(top.e)
-        _lib.check(_lib.lib().emg3d_dev_copy(_ptr(e_fwd), _ptr(top.e), top.e.numel() * top.e.element_size(), _stream()),
-                   'emg3d_dev_copy')
-        meta = Field(grid, frequency=freq)
-        synthetic = fields.get_responses(meta, e_fwd, rec, 'linear', magnetic=mag)
-        obs = np.asarray(observed[(sname, fname)])
-        w = np.ones(obs.shape) if weights is None else np.asarray(weights[(sname, fname)], dtype=float)
-        residual = synthetic - obs
-        have = ~np.isnan(residual)
-        misfit += float(np.sum(w[have] * (residual[have].conj() * residual[have])).real) / 2
-        if not np.any(have & (residual != 0)):
-            # no data (or a perfect fit) for this pair: no residual source, nothing back-propagated,
-            # no contribution (the reference drops such pairs, emg3d/simulations.py:1120-1190)
-            info[(sname, fname)] = {'forward': finfo, 'backward': None, 'synthetic': synthetic}
-            continue
-        rfield = residual_source_field(grid, freq, receivers, residual, w, mag)
-        _, binfo = solver.solve(gmodel, rfield, return_info=True, always_return=True, hierarchy=hier, _download=False,
-                                _sparse_source=True, **{**opts, 'tol': tol_gradient})
-        smu0 = complex(sfield.smu0)
-        o1, o2 = grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
-        if plan is None:
-            gtarget, nc = grad, ncell
-        else:                                          # cell gradient on the computational grid first
-            nc = grid.n_cells
-            gtarget = torch.empty(3 * nc, dtype=torch.float64, device=dev)
-            _lib.check(_lib.lib().emg3d_dev_zero(_ptr(gtarget), gtarget.numel() * 8, _stream()), 'emg3d_dev_zero')
-        _lib.check(_lib.lib().emg3d_dev_gradient_accumulate(
-            nx, ny, nz, int(top.is_complex), _ptr(e_fwd), _ptr(e_fwd, o1), _ptr(e_fwd, o2),
-            _ptr(top.e), _ptr(top.e, o1), _ptr(top.e, o2), smu0.real, smu0.imag, _ptr(vol),
-            _ptr(gtarget), _ptr(gtarget, nc), _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_gradient_accumulate')
-        if plan is not None:                           # ... and back to the model grid: grad += P^T g
-            for k in range(3):
-                plan.adjoint_add(gtarget[k * nc:(k + 1) * nc], grad[k * ncell:(k + 1) * ncell])
-        info[(sname, fname)] = {'forward': finfo, 'backward': binfo, 'synthetic': synthetic}
-    # the one collective of the path: sum over the ranks
-    tm = torch.tensor([misfit], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist = parallel._dist()
-        cdev = dev if dist.get_backend() == 'nccl' else torch.device('cpu')
-        g, m = grad.to(cdev), tm.to(cdev)
-        dist.all_reduce(g)
-        dist.all_reduce(m)
-        grad, tm = g, m
-    misfit = float(tm.cpu()[0])
-    g3 = np.stack([grad[k * ncell:(k + 1) * ncell].cpu().numpy().reshape(mgrid.shape_cells, order='F') for k in range(3)])
+_NCOMP = {'isotropic': 1, 'HTI': 2, 'VTI': 2, 'triaxial': 3}
+_EXPAND = {'isotropic': (0, 0, 0), 'HTI': (0, 1, 0), 'VTI': (0, 0, 1), 'triaxial': (0, 1, 2)}
 
-    # anisotropy bookkeeping + derivative chain of the mapping (simulations.py:1070-1090)
+
+def _vector_components(model, vector):
+    """The model-shaped ``vector`` of ``jvec`` as (n, nx, ny, nz) floats after the derivative chain of the
+    mapping, ``vector_k * d sigma / d property_k`` -- n = 1 (isotropic), 2 (HTI: x, y; VTI: x, z) or 3."""
+    n, shape = _NCOMP[model.case], tuple(model.grid.shape_cells)
+    v = np.asarray(vector)
+    allowed = [(n,) + shape] + ([shape] if n == 1 else [])
+    if v.shape not in allowed or np.iscomplexobj(v):
+        raise ValueError(f"`vector` must be real with shape {' or '.join(str(a) for a in allowed[::-1])} "
+                         f"for a model of case '{model.case}'. Provided: {v.dtype} {v.shape}.")
+    v = np.array(v, dtype=np.float64).reshape((n,) + shape)
+    props = {'isotropic': ('property_x',), 'HTI': ('property_x', 'property_y'), 'VTI': ('property_x', 'property_z'),
+             'triaxial': ('property_x', 'property_y', 'property_z')}[model.case]
+    chain = _DCHAIN[model.mapping]
+    return np.stack([chain(v[k], np.asarray(getattr(model, name), dtype=float)) for k, name in enumerate(props)])
+
+
+def expand_vector(model, vector):
+    """What ``jvec`` hands to ``G``: ``vector`` after the derivative chain of the mapping, expanded to the
+    three conductivity components (3, nx, ny, nz) -- isotropic (v, v, v), HTI (v0, v1, v0), VTI (v0, v0, v1),
+    tri-axial as given (emg3d/simulations.py:1314-1349)."""
+    comps = _vector_components(model, vector)
+    return comps[list(_EXPAND[model.case])]
+
+
+def _finish_gradient(model, g3):
+    """Anisotropy bookkeeping + derivative chain of the mapping (simulations.py:1070-1090) for the gradient
+    with respect to the three conductivity components, (3, nx, ny, nz)."""
     chain = _DCHAIN[model.mapping]
     keep = [0]
     if model.case in ('HTI', 'triaxial'):
@@ -205,5 +175,373 @@ def misfit_and_gradient(model, sources, frequencies, receivers, observed, weight
     else:
         g3[0] += g3[2]
     g3[0] = chain(g3[0], model.property_x)
-    return misfit, np.asfortranarray(g3[keep].squeeze()), info
+    return np.asfortranarray(g3[keep].squeeze())
 
+
+class Sensitivity:
+    """One linearisation point: model, survey geometry, and the forward fields of its pairs.
+
+    Parameters as ``misfit_and_gradient`` (sources, frequencies, receivers, solver_opts, tol_gradient, costs,
+    grids, interpolate_opts, magnetic), plus
+
+    keep: where the forward field of a pair lives between calls -- ``'device'`` (an HBM tensor,
+        ``n_edges x 16 B`` per pair of this rank: 0.8 GB at 256^3), ``'host'`` (a pinned host buffer,
+        uploaded when used) or ``False`` (recomputed by every call: what ``misfit_and_gradient`` costs).
+    batch: > 1: up to that many of the rank's pairs that share frequency and computational grid are solved
+        TOGETHER by ``solver.solve_batch`` in ``jvec`` and ``jtvec`` (multigrid: bit-identical to pair by
+        pair; BiCGSTAB: each source its own iteration, equal to the tolerance). Pairs with magnetic
+        receivers, cgs and gcrotmk stay pair by pair.
+
+    With an initialised process group the pairs are sharded over the ranks at construction (kept fields stay
+    on the rank that owns the pair); ``jvec`` and ``synthetic`` are complete on every rank, ``jtvec`` is
+    all-reduced. ``n_solves`` counts the solves this rank ran: ``{'forward', 'jvec', 'jtvec'}``.
+    """
+
+    def __init__(self, model, sources, frequencies, receivers, solver_opts=None, tol_gradient=1e-5, costs=None,
+                 grids=None, interpolate_opts=None, magnetic=None, keep='device', batch=1):
+        from emg3d_amd import parallel
+        _check_model(model)
+        if keep not in ('device', 'host', False, None):
+            raise ValueError(f"`keep` must be 'device', 'host' or False. Provided: {keep!r}.")
+        self.model, self.sources, self.frequencies = model, dict(sources), dict(frequencies)
+        self.receivers = np.asarray(receivers, dtype=float)
+        self.opts = dict(solver_opts or {})
+        self.opts.setdefault('sslsolver', True)
+        self.tol_gradient = tol_gradient
+        self.grids, self.interpolate_opts = grids, interpolate_opts
+        self.keep = keep or False
+        self.batch = max(1, int(batch))
+        self._rec = _receiver_tuple(self.receivers)
+        nrec = len(self._rec[0])
+        self._mag = np.zeros(nrec, dtype=bool) if magnetic is None else np.asarray(magnetic, dtype=bool)
+        self.pairs = parallel.srcfreq_pairs(self.sources, self.frequencies)
+        self.rank, self.world = parallel.rank_and_world()
+        self._mine = parallel.shard(len(self.pairs), self.rank, self.world, costs)
+        forder = {f: n for n, f in enumerate(self.frequencies)}
+        # pairs of one frequency next to each other: every hierarchy is built once per call
+        self._order = sorted(self._mine, key=lambda i: (forder[self.pairs[i][1]], i))
+        self.n_solves = {'forward': 0, 'jvec': 0, 'jtvec': 0}
+        self.info = {}
+        self._reset()
+
+    def _reset(self):
+        self._kept = {}              # pair index -> forward field (device tensor / pinned host tensor)
+        self._synthetic = {}         # pair index -> responses of the forward field (this rank's pairs)
+        self._all_synthetic = None
+        self._hier = {}              # (s, grid key, batch) -> Hierarchy; one (frequency, grid) at a time
+        self._on_grid = {}
+        self._have_forward = False
+
+    def __repr__(self):
+        return (f"Sensitivity: {len(self.pairs)} pairs ({len(self._mine)} on rank {self.rank} of {self.world}); "
+                f"keep={self.keep!r}, batch={self.batch}; kept forward fields: {len(self._kept)} x "
+                f"{self.kept_bytes // max(len(self._kept), 1):,} B = {self.kept_bytes:,} B "
+                f"({ {'device': 'HBM', 'host': 'pinned host memory'}.get(self.keep, 'nothing kept') })")
+
+    @property
+    def kept_bytes(self):
+        """Bytes held by the kept forward fields of this rank (n_pairs_on_rank x n_edges x 16 B, complex)."""
+        return int(sum(t.numel() * t.element_size() for t in self._kept.values()))
+
+    def release(self):
+        """Drop the kept fields, the hierarchies and the per-grid tables."""
+        self._reset()
+
+    # ----------------------------------------------------------------------------- pieces ---
+    def _device(self):
+        import torch
+        from emg3d_amd import _lib
+        _lib.require_gpu()
+        return torch.device('cuda', torch.cuda.current_device())
+
+    def _computational(self, pair):
+        """(grid key, grid, model on it, cell volumes in HBM, averaging plan or None) of a pair."""
+        import torch
+        mgrid = self.model.grid
+        g = self.grids.get(pair) if isinstance(self.grids, dict) else self.grids
+        if g is None or g == mgrid:
+            g = mgrid
+        key = id(g) if g is not mgrid else 0
+        if key not in self._on_grid:
+            vol = torch.from_numpy(np.ascontiguousarray(g.cell_volumes, dtype=np.float64)).to(self._device())
+            plan = None if g is mgrid else models._VolumeAverage(mgrid, g)
+            self._on_grid[key] = (g, self.model.interpolate_to_grid(g, **(self.interpolate_opts or {})), vol, plan)
+        return (key,) + self._on_grid[key]
+
+    def _hierarchy(self, gkey, gmodel, meta, batch=1):
+        from emg3d_amd import solver
+        hkey = (complex(meta.sval), gkey, batch)
+        hier = self._hier.get(hkey)
+        if hier is None:
+            if any(k[:2] != hkey[:2] for k in self._hier):
+                self._hier.clear()                    # one (frequency, grid) at a time in HBM
+            hier = self._hier[hkey] = solver.Hierarchy(models.VolumeModel(gmodel, meta), batch=batch)
+        return hier
+
+    def _solve_forward(self, i):
+        """Forward solve of pair i: (field in HBM -- a copy, the hierarchy's own buffer is reused --, responses)."""
+        import torch
+        from emg3d_amd import _lib, solver
+        from emg3d_amd._device import _ptr, _stream
+        sname, fname = self.pairs[i]
+        freq = self.frequencies[fname]
+        gkey, grid, gmodel, vol, plan = self._computational((sname, fname))
+        sfield = fields.get_source_field(grid, self.sources[sname], freq)
+        hier = self._hierarchy(gkey, gmodel, sfield)
+        top = hier.top
+        _, finfo = solver.solve(gmodel, sfield, return_info=True, always_return=True, hierarchy=hier, _download=False,
+                                _sparse_source=True, **self.opts)
+        self.n_solves['forward'] += 1
+        e_fwd = torch.empty_like(top.e)
+        _lib.check(_lib.lib().emg3d_dev_copy(_ptr(e_fwd), _ptr(top.e), top.e.numel() * top.e.element_size(), _stream()),
+                   'emg3d_dev_copy')
+        synthetic = fields.get_responses(Field(grid, frequency=freq), e_fwd, self._rec, 'linear', magnetic=self._mag)
+        self.info.setdefault((sname, fname), {}).update(forward=finfo, backward=None, synthetic=synthetic)
+        return e_fwd, synthetic
+
+    def _forward_field(self, i):
+        """Forward field of pair i in HBM and its responses: the kept one, or a new solve (``keep=False``)."""
+        import torch
+        if i in self._kept:
+            e = self._kept[i]
+            if self.keep == 'host':
+                e = e.to(self._device(), non_blocking=False)
+            return e, self._synthetic[i]
+        e, synthetic = self._solve_forward(i)
+        self._synthetic[i] = synthetic
+        if self.keep == 'device':
+            self._kept[i] = e
+        elif self.keep == 'host':
+            pinned = torch.empty(e.shape, dtype=e.dtype, pin_memory=True)
+            pinned.copy_(e)
+            self._kept[i] = pinned
+        return e, synthetic
+
+    def forward(self):
+        """Forward solves of this rank's pairs at ``solver_opts['tol']`` (once; later calls return at once, and
+        with ``keep=False`` only the responses are kept)."""
+        if not self._have_forward:
+            for i in self._order:
+                self._forward_field(i)
+            self._have_forward = True
+        return self
+
+    @property
+    def synthetic(self):
+        """Forward responses: dict (src, freq) -> complex array (n_receivers), complete on every rank."""
+        if self._all_synthetic is None:
+            self.forward()
+            self._all_synthetic = self._gather({self.pairs[i]: self._synthetic[i] for i in self._mine})
+        return self._all_synthetic
+
+    def _gather(self, local):
+        """The union of the ranks' small dicts, on every rank, in the order of ``pairs``."""
+        if self.world > 1:
+            from emg3d_amd import parallel
+            parts = [None] * self.world
+            parallel._dist().all_gather_object(parts, local)
+            local = {k: v for part in parts for k, v in part.items()}
+        return {p: local[p] for p in self.pairs if p in local}
+
+    def _chunks(self):
+        """This rank's pairs in solve order, grouped for ``solve_batch``: lists of up to ``batch`` pair indices
+        that share frequency and computational grid (lists of one: pair by pair)."""
+        batched = (self.batch > 1 and not self._mag.any() and
+                   self.opts.get('sslsolver', True) in (True, False, None, 'bicgstab') and
+                   self.opts.get('cycle', 'F') is not None)
+        chunks = []
+        for i in self._order:
+            key = (self.pairs[i][1], self._computational(self.pairs[i])[0])
+            if batched and chunks and chunks[-1][0] == key and len(chunks[-1][1]) < self.batch:
+                chunks[-1][1].append(i)
+            else:
+                chunks.append((key, [i]))
+        return [c for _, c in chunks]
+
+    # ------------------------------------------------------------------------------- jvec ---
+    def jvec(self, vector):
+        """Sensitivity times a model-shaped real ``vector`` -- shape (nx, ny, nz) or (1, ...) isotropic,
+        (2, ...) HTI / VTI, (3, ...) tri-axial, as ``Simulation.jvec``: dict (src, freq) -> complex array
+        (n_receivers), complete on every rank. One solve per pair at ``tol_gradient``; a zero vector gives
+        zeros without a solve."""
+        import torch
+        from emg3d_amd import _lib, solver
+        from emg3d_amd._device import _ptr, _stream
+        comps = _vector_components(self.model, vector)          # raises on a wrong shape, before any GPU work
+        dev = self._device()
+        expand = _EXPAND[self.model.case]
+        # (cells x fastest, as the kernels index them; the transposition of a C-ordered array runs on the device)
+        on_model = [torch.from_numpy(np.ascontiguousarray(c)).to(dev).permute(2, 1, 0).contiguous().reshape(-1)
+                    for c in comps]
+        regridded = {0: on_model}
+        opts = {**self.opts, 'tol': self.tol_gradient}
+        out = {}
+        for chunk in self._chunks():
+            nb = len(chunk)
+            sname, fname = self.pairs[chunk[0]]
+            freq = self.frequencies[fname]
+            gkey, grid, gmodel, vol, plan = self._computational((sname, fname))
+            if gkey not in regridded:            # linear volume average: the map whose adjoint is jtvec's way back
+                regridded[gkey] = [plan.on_device(c, log=False) for c in on_model]
+            vx, vy, vz = (regridded[gkey][k] for k in expand)
+            meta = Field(grid, frequency=freq)
+            smu0 = complex(meta.smu0)
+            nx, ny, nz = grid.shape_cells
+            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
+            forward = [self._forward_field(i)[0] for i in chunk]      # (before the batch hierarchy replaces another)
+            hier = self._hierarchy(gkey, gmodel, meta, nb)
+            top = hier.top
+            for b, e in enumerate(forward):
+                _lib.check(_lib.lib().emg3d_dev_sensitivity_source(
+                    nx, ny, nz, int(top.is_complex), _ptr(e), _ptr(e, o1), _ptr(e, o2), smu0.real, smu0.imag,
+                    _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(top.s, b * n), _ptr(top.s, b * n + o1),
+                    _ptr(top.s, b * n + o2), _stream()), 'emg3d_dev_sensitivity_source')
+            del forward
+            if nb == 1:
+                _, info = solver.solve(gmodel, meta, return_info=True, always_return=True, hierarchy=hier,
+                                       _download=False, _device_source=True, **opts)
+                infos = [info]
+                resp = [fields.get_responses(meta, top.e, self._rec, 'linear', magnetic=self._mag)]
+            else:
+                res = solver.solve_batch(gmodel, [Field(grid, frequency=freq) for _ in chunk], receivers=self._rec,
+                                         receiver_method='linear', keep_fields=False, hierarchy=hier,
+                                         _device_sources=True, **opts)
+                infos = [info for _, info in res]
+                resp = [np.asarray(info['responses']) for info in infos]
+            for i, info, r in zip(chunk, infos, resp):
+                self.n_solves['jvec'] += int(not np.isnan(info['ref_error']))     # (NaN: zero source, nothing solved)
+                self.info.setdefault(self.pairs[i], {})['jvec'] = info
+                out[self.pairs[i]] = np.asarray(r)
+        return self._gather(out)
+
+    # ------------------------------------------------------------------------------ jtvec ---
+    def jtvec(self, vector):
+        """Adjoint of the sensitivity times a data-shaped ``vector`` -- dict (src, freq) -> complex array
+        (n_receivers), NaN or a missing pair: no datum --: real array shaped like the gradient of
+        ``misfit_and_gradient``, with ``sum(v * jtvec(y)) == Re sum conj(y) * jvec(v)``. One solve per pair at
+        ``tol_gradient`` against the kept forward field; all-reduced over the ranks."""
+        nrec = len(self._rec[0])
+        for pair, y in vector.items():
+            if np.shape(y) != (nrec,):
+                raise ValueError(f"`vector[{pair!r}]` must have shape ({nrec},): one value per receiver. "
+                                 f"Provided: {np.shape(y)}.")
+
+        def data(pair, synthetic):
+            y = vector.get(pair)
+            return (None, None) if y is None else (np.asarray(y), np.ones(nrec))      # (real in the Laplace domain)
+        return self._back_propagate(data)[1]
+
+    def misfit_and_gradient(self, observed, weights=None):
+        """Misfit ``sum w |synthetic - observed|^2 / 2`` and its gradient ``jtvec((synthetic - observed) w)``,
+        from the kept forward fields."""
+        def data(pair, synthetic):
+            obs = np.asarray(observed[pair])
+            w = np.ones(obs.shape) if weights is None else np.asarray(weights[pair], dtype=float)
+            return synthetic - obs, w
+        return self._back_propagate(data, with_misfit=True)
+
+    def _back_propagate(self, data, with_misfit=False):
+        """``data(pair, synthetic) -> (residual, weight)`` per receiver: steps 3-8 of the module docstring for
+        this rank's pairs. Returns (misfit of the residuals if asked for, gradient)."""
+        import torch
+        from emg3d_amd import _lib, parallel, solver
+        from emg3d_amd._device import _ptr, _stream
+        dev = self._device()
+        mgrid = self.model.grid
+        ncell = mgrid.n_cells
+        grad = torch.zeros(3 * ncell, dtype=torch.float64, device=dev)
+        misfit = 0.0
+        opts = {**self.opts, 'tol': self.tol_gradient}
+        for chunk in self._chunks():
+            sname, fname = self.pairs[chunk[0]]
+            freq = self.frequencies[fname]
+            gkey, grid, gmodel, vol, plan = self._computational((sname, fname))
+            nx, ny, nz = grid.shape_cells
+            forward, rfields = [], []
+            for i in chunk:
+                pair = self.pairs[i]
+                e_fwd, synthetic = self._forward_field(i)
+                residual, w = data(pair, synthetic)
+                rfield = None
+                if residual is not None:
+                    have = ~np.isnan(residual)
+                    if with_misfit:
+                        misfit += float(np.sum(w[have] * (residual[have].conj() * residual[have])).real) / 2
+                    # no data (or a perfect fit) for this pair: no residual source, nothing back-propagated,
+                    # no contribution (the reference drops such pairs, emg3d/simulations.py:1120-1190)
+                    if np.any(have & (residual != 0)):
+                        rfield = residual_source_field(grid, freq, self.receivers, residual, w, self._mag)
+                forward.append(e_fwd)
+                rfields.append(rfield)
+            live = [b for b, rf in enumerate(rfields) if rf is not None]
+            if not live:
+                continue
+            meta = Field(grid, frequency=freq)
+            if len(live) == 1:
+                hier = self._hierarchy(gkey, gmodel, meta)
+                _, binfo = solver.solve(gmodel, rfields[live[0]], return_info=True, always_return=True, hierarchy=hier,
+                                        _download=False, _sparse_source=True, **opts)
+                back = {live[0]: (hier.top.e, binfo)}
+            else:
+                for b in live:
+                    rfields[b]._trust_sparse = True
+                hier = self._hierarchy(gkey, gmodel, meta, len(live))
+                res = solver.solve_batch(gmodel, [rfields[b] for b in live], keep_fields=False, hierarchy=hier,
+                                         _device_fields=True, **opts)
+                back = {b: (info['_device_field'], info) for b, (_, info) in zip(live, res)}
+            top = hier.top
+            smu0 = complex(meta.smu0)
+            o1, o2 = grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
+            for b in live:
+                bfield, binfo = back[b]
+                self.n_solves['jtvec'] += 1
+                binfo.pop('_device_field', None)
+                self.info.setdefault(self.pairs[chunk[b]], {})['backward'] = binfo
+                if bfield is None:                         # the solve failed: zero field, no contribution
+                    continue
+                e_fwd = forward[b]
+                if plan is None:
+                    gtarget, nc = grad, ncell
+                else:                                          # cell gradient on the computational grid first
+                    nc = grid.n_cells
+                    gtarget = torch.empty(3 * nc, dtype=torch.float64, device=dev)
+                    _lib.check(_lib.lib().emg3d_dev_zero(_ptr(gtarget), gtarget.numel() * 8, _stream()), 'emg3d_dev_zero')
+                _lib.check(_lib.lib().emg3d_dev_gradient_accumulate(
+                    nx, ny, nz, int(top.is_complex), _ptr(e_fwd), _ptr(e_fwd, o1), _ptr(e_fwd, o2),
+                    _ptr(bfield), _ptr(bfield, o1), _ptr(bfield, o2), smu0.real, smu0.imag, _ptr(vol),
+                    _ptr(gtarget), _ptr(gtarget, nc), _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_gradient_accumulate')
+                if plan is not None:                           # ... and back to the model grid: grad += P^T g
+                    for k in range(3):
+                        plan.adjoint_add(gtarget[k * nc:(k + 1) * nc], grad[k * ncell:(k + 1) * ncell])
+            del forward, back
+        # the one collective of the path: sum over the ranks
+        tm = torch.tensor([misfit], dtype=torch.float64, device=dev)
+        if self.world > 1:
+            dist = parallel._dist()
+            cdev = dev if dist.get_backend() == 'nccl' else torch.device('cpu')
+            g, m = grad.to(cdev), tm.to(cdev)
+            dist.all_reduce(g)
+            dist.all_reduce(m)
+            grad, tm = g, m
+        misfit = float(tm.cpu()[0])
+        g3 = np.stack([grad[k * ncell:(k + 1) * ncell].cpu().numpy().reshape(mgrid.shape_cells, order='F')
+                       for k in range(3)])
+        return misfit, _finish_gradient(self.model, g3)
+
+
+def jvec(model, vector, sources, frequencies, receivers, **kwargs):
+    """One-shot ``Sensitivity(model, sources, frequencies, receivers, **kwargs).jvec(vector)``."""
+    lin = Sensitivity(model, sources, frequencies, receivers, **kwargs)
+    try:
+        return lin.jvec(vector)
+    finally:
+        lin.release()
+
+
+def jtvec(model, vector, sources, frequencies, receivers, **kwargs):
+    """One-shot ``Sensitivity(model, sources, frequencies, receivers, **kwargs).jtvec(vector)``."""
+    lin = Sensitivity(model, sources, frequencies, receivers, **kwargs)
+    try:
+        return lin.jtvec(vector)
+    finally:
+        lin.release()

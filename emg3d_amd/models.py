@@ -146,13 +146,21 @@ class _VolumeAverage:
         from emg3d_amd import _lib
         from emg3d_amd._device import _ptr, _stream
         v = torch.from_numpy(np.ascontiguousarray(values.ravel('F'))).to(self.dev)
+        return self.on_device(v, log).cpu().numpy().reshape(self.shape_out, order='F')
+
+    def on_device(self, v, log=False):
+        """Device in, device out: ``v`` (cells of the original grid, F-order, doubles) -> the averages on
+        the new grid as a device tensor (the sensitivity products re-grid their vector per pair)."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
         out = torch.empty(int(np.prod(self.shape_out)), dtype=torch.float64, device=self.dev)
         (sx, wx, ix), (sy, wy, iy), (sz, wz, iz) = self.tabs
         _lib.check(_lib.lib().emg3d_dev_volume_average(
             _ptr(v), *self.shape_in, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(wx), _ptr(wy), _ptr(wz),
             _ptr(ix), _ptr(iy), _ptr(iz), _ptr(self.vol), *self.shape_out, _ptr(out), int(bool(log)), _stream()),
             'emg3d_dev_volume_average')
-        return out.cpu().numpy().reshape(self.shape_out, order='F')
+        return out
 
     def adjoint_add(self, nval, oval):
         """oval += P^T nval for device arrays: ``nval`` on the new grid (cells, F-order), ``oval`` on

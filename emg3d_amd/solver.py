@@ -43,6 +43,7 @@ def __dir__():
 _SOLVE_EXTRAS = {'always_return': False, 'plain': False, 'efield': None, 'hierarchy': None,
                  '_download': True,           # False: the result stays in hierarchy.top.e only
                  '_sparse_source': False,     # the source goes up as its few non-zeros
+                 '_device_source': False,     # the source is in hierarchy.top.s already (gradient.Sensitivity.jvec)
                  'smoother_omega': 1.0,       # != 1: extrapolated smoothing calls (_cycle.smooth_level)
                  'residual_form': 'auto',     # finest level in residual form (_cycle.run_cycles)
                  'line_compact': None}        # Hierarchy(line_compact=): compact records of the streamed line passes
@@ -154,7 +155,16 @@ def solve(model, sfield, sslsolver=True, semicoarsening=True, linerelaxation=Tru
     if var.sparse_source and not extra['_sparse_source']:
         sfield._assemble_on_device = False
     var.download = bool(extra['_download'])
-    var.l2_refe = _host_norm(sfield._sparse[1] if var.sparse_source else sfield.field)
+    var.device_source = bool(extra['_device_source'])
+    if var.device_source:
+        # `sfield` only describes grid and frequency: the values were formed on the device, in the hierarchy's source
+        # vector, and so is their norm
+        if extra['hierarchy'] is None or extra['hierarchy'].top.batch != 1 or extra['efield'] is not None:
+            raise ValueError("`_device_source` needs `hierarchy=` (batch 1) and no start field.")
+        var.sparse_source = False
+        var.l2_refe = float(_device_source_norms(extra['hierarchy'].top))
+    else:
+        var.l2_refe = _host_norm(sfield._sparse[1] if var.sparse_source else sfield.field)
     var.error_at_cycle[0] = var.l2_refe
 
     vmodel = models.VolumeModel(model, sfield)
@@ -185,6 +195,15 @@ def solve(model, sfield, sslsolver=True, semicoarsening=True, linerelaxation=Tru
     if var.return_info:
         out.append(_info_dict(var))
     return out[0] if len(out) == 1 else (tuple(out) if out else None)
+
+
+def _device_source_norms(top):
+    """2-norm of the source vector(s) that are in ``top.s`` (one per right-hand side for a batch): the
+    residual of the zero field is the source. Leaves ``top.e`` zero."""
+    if getattr(top, '_resmode', None) is not None:      # (left behind by an interrupted solve)
+        top._resmode = None
+    top.zero_field()
+    return top.residual(store=False, norm=True)
 
 
 def _nothing_to_do(var, note):
@@ -305,6 +324,9 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
     omega = _check_omega(kwargs.pop('smoother_omega', 1.0))     # extrapolated smoothing calls, as in solve()
     resform = kwargs.pop('residual_form', 'auto')               # finest level in residual form, as in solve()
     line_compact = kwargs.pop('line_compact', None)             # Hierarchy(line_compact=), as in solve()
+    device_sources = bool(kwargs.pop('_device_sources', False))  # the sources are in hierarchy.top.s already (and
+    #                                                              `sfields` only describe grid and frequency)
+    device_fields = bool(kwargs.pop('_device_fields', False))    # info['_device_field']: the solution in HBM (or None)
     sfields = list(sfields)
     nb = len(sfields)
     if nb == 0:
@@ -334,6 +356,9 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
             return None
         return receivers[b] if isinstance(receivers, list) else receivers
 
+    if device_sources and (nb == 1 or var.clevel[var.sc_dir] == 0 or hierarchy is None or hierarchy.top.batch != nb):
+        raise ValueError("solve_batch: `_device_sources` needs `hierarchy=` with one slot per source, more than one "
+                         "source and a grid that can be coarsened.")
     if nb == 1 or var.clevel[var.sc_dir] == 0:
         out = []
         for b, sf in enumerate(sfields):
@@ -355,7 +380,12 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
         v.hierarchy_compact = hier.line_compact
     n = top.grid.n_edges
     efields = []
-    for b, (sf, v) in enumerate(zip(sfields, vars_)):
+    if device_sources:
+        for sf, v, norm in zip(sfields, vars_, _device_source_norms(top)):
+            v.l2_refe = float(norm)
+            v.error_at_cycle[0] = v.l2_refe
+            efields.append(fields.Field(model.grid, dtype=sf.dtype, frequency=sf._frequency))
+    for b, (sf, v) in enumerate(() if device_sources else zip(sfields, vars_)):
         sparse = getattr(sf, '_sparse', None) is not None and (bool(getattr(sf, '_trust_sparse', False)) or
                                                                getattr(sf, '_untouched', False))
         if sparse and not getattr(sf, '_trust_sparse', False):
@@ -379,6 +409,8 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
         elif keep_fields and done[b] is not None:
             torch.from_numpy(ef.field).copy_(done[b])
         info = _info_dict(v)
+        if device_fields:
+            info['_device_field'] = None if zero else done[b]
         if rec_of(b) is not None:     # from the solution while it is in HBM
             info['responses'] = fields.get_receiver(ef, rec_of(b), receiver_method,
                                                     device_field=None if zero or done[b] is None else done[b])
@@ -685,7 +717,10 @@ def multigrid(model, sfield, efield, var, **kwargs):
     hier = kwargs.get('hierarchy') or Hierarchy(model, line_compact=getattr(var, 'line_compact', None),
                                                 point_compact_top=bool(getattr(var, 'residual_form', False)))
     var.hierarchy_compact = hier.line_compact
-    hier.upload(sfield, efield, getattr(var, 'sparse_source', False))
+    if getattr(var, 'device_source', False):
+        hier.upload_field(efield)
+    else:
+        hier.upload(sfield, efield, getattr(var, 'sparse_source', False))
     try:
         _multigrid(hier.top, var, 0, 0)
     finally:
@@ -769,7 +804,11 @@ def _krylov_on_device(method, hier, sfield, efield, var):
     back into ``efield`` -- and into ``hier.top.e``, where receivers are read from."""
     top = hier.top
     b = torch.empty(top.e.numel(), dtype=top.e.dtype, device=hier.device)
-    hier.put_source(sfield, b, getattr(var, 'sparse_source', False))
+    if getattr(var, 'device_source', False):
+        _lib.check(_lib.lib().emg3d_dev_copy(b.data_ptr(), top.s.data_ptr(), b.numel() * b.element_size(),
+                                             torch.cuda.current_stream().cuda_stream), 'emg3d_dev_copy')
+    else:
+        hier.put_source(sfield, b, getattr(var, 'sparse_source', False))
     x = torch.empty_like(b)
     if getattr(efield, '_is_zero', False):
         _lib.check(_lib.lib().emg3d_dev_zero(x.data_ptr(), x.numel() * x.element_size(),

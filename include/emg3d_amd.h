@@ -390,6 +390,20 @@ int emg3d_dev_gradient_accumulate(int nx, int ny, int nz, int is_complex, const 
                                   double smu0_re, double smu0_im, const double *volumes, double *gx,
                                   double *gy, double *gz, void *stream);
 
+/* ---- sensitivity products: the source of Simulation.jvec (emg3d/simulations.py:1352-1362) -----
+ * The transpose of emg3d_dev_gradient_accumulate: a model perturbation v* (cells, doubles, one array
+ * per component; vy / vz may alias vx) becomes a source field on the edges,
+ *     g = -s mu0 * e * 1/4 * sum over the (up to four) cells that share the edge of volumes * v
+ * (the reference takes the operator from discretize's get_edge_inner_product_deriv). g* is WRITTEN
+ * (every edge, not accumulated) and may be any device buffer laid out like a field -- in practice a
+ * level's source vector, or slice b of it for a batch. Fixed summation order (cells z outer, y, x
+ * inner), no atomics. For any fields e, b and real v:
+ *     sum_cells v_k * gradient_accumulate(e, b)_k == -Re sum_edges b * sensitivity_source(e, v). */
+int emg3d_dev_sensitivity_source(int nx, int ny, int nz, int is_complex, const void *ex, const void *ey,
+                                 const void *ez, double smu0_re, double smu0_im, const double *volumes,
+                                 const double *vx, const double *vy, const double *vz, void *gx, void *gy,
+                                 void *gz, void *stream);
+
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid
  * (emg3d/models.py:322-366). values (nx,ny,nz) -> out (mx,my,mz), doubles, x fastest. Per axis
