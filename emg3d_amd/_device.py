@@ -469,9 +469,13 @@ class DeviceLevel:
                    'emg3d_dev_zero')
 
     def pec_zero(self):
+        """Zero the tangential components of e on the six boundary faces, for every right-hand side of the level."""
         nx, ny, nz = self.grid.shape_cells
-        _lib.check(_lib.lib().emg3d_dev_pec_zero(*self.parts(self.e), nx, ny, nz,
-                                                 self.is_complex, _stream()), 'emg3d_dev_pec_zero')
+        n = self.grid.n_edges
+        for b in range(self.batch):      # (the kernel takes one field: source b lives at b * n_edges)
+            _lib.check(_lib.lib().emg3d_dev_pec_zero(_ptr(self.e, b * n), _ptr(self.e, b * n + self._o1),
+                                                     _ptr(self.e, b * n + self._o2), nx, ny, nz,
+                                                     self.is_complex, _stream()), 'emg3d_dev_pec_zero')
 
     # ------------------------------------------------------------- grid transfer ------
     def child(self, sc_dir):

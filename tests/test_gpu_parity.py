@@ -20,7 +20,8 @@ from emg3d_amd import core, solver, _lib
 from emg3d_amd._device import DeviceLevel
 from oracle import core as ocore
 from oracle import mg_ref
-from helpers import relerr, widths
+from helpers import (admissible_sc_dirs, coarse_grid, pec_mask, random_field, random_level, relerr, sc_factors,
+                     widths)
 
 pytestmark = pytest.mark.gpu
 
@@ -997,28 +998,93 @@ def test_line_lpw_option_on_long_lines_vs_default(lpw):
     assert np.array_equal(out[lpw], out[0])
 
 
-@pytest.mark.parametrize('shape,kw', [
+RAGGED_SOLVES = [
     ((48, 32, 24), dict(cycle='W', semicoarsening=True, linerelaxation=True)),
     ((24, 40, 16), dict(cycle='V', semicoarsening=2, linerelaxation=2)),
     ((20, 12, 36), dict(cycle='F', semicoarsening=False, linerelaxation=7, clevel=1)),
-])
-def test_solve_ragged_grids_vs_oracle(shape, kw):
-    """Non-cubic grids whose coarsest levels are odd (3, 5, 9 cells) or stop early: GPU
-    vs oracle (lexicographic) converged fields, tri-axial random model."""
+]
+
+
+def _ragged_problem(shape, freq=0.8, sources=((3., -2., 1., 20., 30.),)):
+    """Stretched non-cubic grid with a random tri-axial model: (grid, model, source fields, oracle volume model)."""
     rng = np.random.default_rng(sum(shape))
     h = [widths(n // 2, n // 4, 20., 1.15) for n in shape]
     grid = emg3d.TensorMesh(h, [-w.sum() / 2 for w in h])
     assert grid.shape_cells == shape
     rho = 10 ** rng.uniform(-0.5, 1.0, shape)
     model = emg3d.Model(grid, rho, 1.5 * rho, 2.5 * rho)
-    sfield = emg3d.get_source_field(grid, (3., -2., 1., 20., 30.), 0.8)
+    sfields = [emg3d.get_source_field(grid, src, freq) for src in sources]
+    ogrid = mg_ref.Grid(grid.h, grid.origin)
+    vm = mg_ref.volume_model(ogrid, freq, 1 / rho, 1 / (1.5 * rho), 1 / (2.5 * rho))
+    return grid, model, sfields, vm
+
+
+@pytest.mark.parametrize('shape,kw', RAGGED_SOLVES)
+def test_solve_ragged_grids_vs_oracle(shape, kw):
+    """Non-cubic grids whose coarsest levels are odd (3, 5, 9 cells) or stop early: GPU
+    vs oracle (lexicographic) converged fields, tri-axial random model; and the cycle count of the oracle's
+    driver in the GPU's own smoother ordering."""
+    grid, model, (sfield,), vm = _ragged_problem(shape)
     e, info = emg3d.solve(model, sfield, sslsolver=False, tol=1e-10, return_info=True, **kw)
     assert info['exit'] == 0, info['exit_message']
-    ogrid = mg_ref.Grid(grid.h, grid.origin)
-    vm = mg_ref.volume_model(ogrid, 0.8, 1 / rho, 1 / (1.5 * rho), 1 / (2.5 * rho))
+    ogrid = vm.grid
     eo, io = mg_ref.solve(vm, mg_ref.Field(ogrid, sfield.field.copy()), tol=1e-10, **kw)
     assert io['exit'] == 0
     assert relerr(e.field, eo.field) < 1e-8
+    _, io1 = mg_ref.solve(vm, mg_ref.Field(ogrid, sfield.field.copy()), tol=1e-10, order=1, **kw)
+    assert io1['exit'] == 0
+    assert info['it_mg'] == io1['it_mg']
+
+
+def _one_cycle_on(model, sfields, vm, **kw):
+    """ONE multigrid cycle (fp64 line records) of `model` for the source field(s) -- a list goes through
+    solve_batch -- on the GPU and with the oracle's driver on its volume model `vm` in the same smoother ordering,
+    with the assertions of the fp64 branch of _one_cycle_vs_oracle: fields after the cycle to 1e-10, residual norms
+    to 1e-9, the same smoother work. A transfer, a coarse model or a residual that is slightly wrong shows here
+    (it does not in a converged field: the fixed point is the same)."""
+    if isinstance(sfields, (list, tuple)):
+        got = emg3d.solve_batch(model, list(sfields), tol=1e-30, maxit=1, line_compact=False, **kw)
+    else:
+        sfields = [sfields]
+        got = [emg3d.solve(model, sfields[0], sslsolver=False, tol=1e-30, maxit=1, return_info=True,
+                           line_compact=False, **kw)]
+    assert len(got) == len(sfields)
+    for b, ((e, info), sf) in enumerate(zip(got, sfields)):
+        eo, io = mg_ref.solve(vm, mg_ref.Field(vm.grid, sf.field.copy()), tol=1e-30, maxit=1, order=1, **kw)
+        assert info['it_mg'] == io['it_mg'] == 1
+        d = relerr(e.field, eo.field)
+        print(f"one cycle {vm.grid.shape_cells} {kw} source {b}: field {d:.2e}, abs_error {info['abs_error']:.6e} "
+              f"(oracle {io['abs_error']:.6e}, rel {abs(info['abs_error'] / io['abs_error'] - 1):.2e})")
+        assert np.linalg.norm(eo.field) > 0 and e.field.dtype == eo.field.dtype
+        assert d < 1e-10, (b, d)
+        assert info['abs_error'] == pytest.approx(io['abs_error'], rel=1e-9), b
+        assert info['smoother_cell_sweeps'] == io['smooth_work'], b
+
+
+@pytest.mark.parametrize('shape,kw', RAGGED_SOLVES)
+def test_ragged_grids_one_cycle_vs_oracle_same_order(shape, kw):
+    """The grids and options of test_solve_ragged_grids_vs_oracle (W-cycle with rotating semicoarsening and line
+    relaxation; V-cycle, y never coarsened, y-lines; F-cycle, three line directions, one coarse level): ONE cycle
+    against the oracle in the same ordering -- coarse levels of odd and 2-cell directions, every transfer of the
+    cycle compared before convergence hides it."""
+    grid, model, (sfield,), vm = _ragged_problem(shape)
+    _one_cycle_on(model, sfield, vm, **kw)
+
+
+def test_ragged_grid_one_cycle_laplace_domain_vs_oracle_same_order():
+    """One F-cycle with semicoarsening and line relaxation in the Laplace domain (real arithmetic: the <double>
+    instantiations of every kernel of the cycle) on the 48 x 32 x 24 grid."""
+    grid, model, (sfield,), vm = _ragged_problem((48, 32, 24), freq=-0.8)
+    assert sfield.field.dtype == np.float64 and vm.eta_x.dtype == np.float64
+    _one_cycle_on(model, sfield, vm, cycle='F', semicoarsening=True, linerelaxation=True)
+
+
+def test_ragged_grid_one_cycle_batch_of_three_vs_oracle_same_order():
+    """solve_batch of three sources on 48 x 32 x 24, one W-cycle: every source against the oracle's cycle for that
+    source alone (the batch strides of the residual, restriction and prolongation launches on every level)."""
+    sources = ((3., -2., 1., 20., 30.), (-40., 25., -10., 70., -15.), (10., 10., 5., 0., 90.))
+    grid, model, sfields, vm = _ragged_problem((48, 32, 24), sources=sources)
+    _one_cycle_on(model, sfields, vm, cycle='W', semicoarsening=True, linerelaxation=True)
 
 
 @pytest.mark.parametrize('shape', [(36, 20, 18), (40, 24, 33)])
@@ -2857,3 +2923,277 @@ def test_extrapolated_smoothing_same_solution_fewer_cycles():
     assert ib2['it_mg'] == i2['it_mg'] and ib3['it_mg'] == i3['it_mg']
     assert np.linalg.norm(b2.field - e2.field) <= 1e-12 * np.linalg.norm(e2.field)
     assert np.linalg.norm(b3.field - e3.field) <= 1e-12 * np.linalg.norm(e3.field)
+
+
+# --- grid transfer, model restriction, residual and operator kernels through DeviceLevel, beyond one workgroup ----
+# (shape, anisotropy case, with epsilon_r / mu_r). The launch block of these kernels is 64 x 4 threads, one plane
+# (and, batched, one right-hand side) per blockIdx.z.
+TRANSFER_SHAPES = [
+    ((130, 6, 10), 'triaxial', False),    # 131 = 2 x 64 + 3 nodes in x (three threads in the last block); coarse: 66
+    ((66, 70, 34), 'VTI', False),         # 67 nodes in x, 71 in y (18 rows of 4, three threads used); the coarse level
+    #                                       (34 nodes in x) fits one block in x, the fine one does not; eta_y aliases eta_x
+    ((10, 9, 130), 'HTI', True),          # odd in y (never coarsened), 131 planes: the batch index from blockIdx.z / planes
+    ((64, 4, 2), 'isotropic', False),     # 65 = 64 + 1 nodes in x (one thread in the last block), a 2-cell direction in z
+    ((2, 258, 6), 'triaxial', True),      # a 2-cell direction in x, 259 nodes in y (65 rows of 4, the last with 3)
+    ((96, 129, 40), 'VTI', False),        # the largest (0.5 M cells): 97 nodes in x, 130 in y, odd in y
+]
+# odd everywhere: no coarsening; residual, operator and PEC kernels only. 64 and 128 nodes in x (last block full)
+ODD_SHAPES = [((63, 5, 7), 'VTI', False), ((127, 11, 3), 'triaxial', True)]
+TRANSFER_BATCHES = (1, 2, 5)
+_SENTINEL = 7.5
+
+
+def _ids(p):
+    return 'x'.join(map(str, p[0])) + '-' + p[1] + ('-extras' if p[2] else '')
+
+
+def _batch_calls(batch, nsrc=5):
+    """Which of the nsrc test sources a level of `batch` right-hand sides is called with: alone, one call each,
+    or the first `batch` together."""
+    return [[b] for b in range(nsrc)] if batch == 1 else [list(range(batch))]
+
+
+def _stack(fields, srcs):
+    return torch.from_numpy(np.concatenate([fields[b].field for b in srcs]))
+
+
+def test_transfer_shapes_cover_the_block_edges():
+    """What TRANSFER_SHAPES / ODD_SHAPES promise: node counts of 64 k, 64 k + 1 and 64 k + 3 in x, y node counts that
+    are and are not a multiple of 4, 2-cell directions, a coarse level inside one block of a fine one that is not, and
+    every semicoarsening code admissible at least three times."""
+    shapes = [s for s, _, _ in TRANSFER_SHAPES + ODD_SHAPES]
+    xn = {(s[0] + 1) % 64 for s in shapes if s[0] + 1 >= 64}
+    assert {0, 1, 3} <= xn
+    assert any((s[1] + 1) % 4 for s in shapes) and any((s[1] + 1) % 4 == 0 for s in shapes)
+    assert any(2 in s for s, _, _ in TRANSFER_SHAPES)
+    assert any(s[0] + 1 > 64 >= s[0] // 2 + 1 for s, _, _ in TRANSFER_SHAPES)
+    count = np.zeros(7, dtype=int)
+    for s, _, _ in TRANSFER_SHAPES:
+        count[admissible_sc_dirs(s)] += 1
+    assert np.all(count >= 3), count
+    assert all(admissible_sc_dirs(s) == [] for s in shapes[len(TRANSFER_SHAPES):])
+    assert {c for _, c, _ in TRANSFER_SHAPES} == {'isotropic', 'VTI', 'HTI', 'triaxial'}
+
+
+@pytest.mark.parametrize('dtype', [complex, float])
+@pytest.mark.parametrize('shape,case,extras', TRANSFER_SHAPES, ids=map(_ids, TRANSFER_SHAPES))
+def test_device_child_model_vs_oracle(shape, case, extras, dtype):
+    """DeviceLevel.child(sc_dir) (k_restrict_param through emg3d_dev_restrict_param: grids of several blocks, ragged
+    last blocks) against the coarse model of mg_ref.restriction, 1e-15, for every semicoarsening code the shape
+    admits and levels of 1, 2 and 5 right-hand sides: summed eta_x / eta_y / eta_z / zeta, their aliasing as the
+    anisotropy case says, the coarse widths, the sizes of the child's field buffers."""
+    grid, vm, rng = random_level(shape, case, dtype, sum(shape), extras=extras, stretch=1.03)
+    levels = [DeviceLevel.from_host(vm, torch.device('cuda'), batch=batch) for batch in TRANSFER_BATCHES]
+    zero = mg_ref.Field(grid, dtype=dtype)
+    for sc_dir, lv in [(sc_dir, lv) for sc_dir in admissible_sc_dirs(shape) for lv in levels]:
+        cmodel = mg_ref.restriction(vm, zero, zero, sc_dir)[0]
+        c = lv.child(sc_dir)['level']
+        assert lv.child(sc_dir)['level'] is c
+        assert c.grid.shape_cells == cmodel.grid.shape_cells == tuple(n // f for n, f in zip(shape, sc_factors(sc_dir)))
+        for d in range(3):
+            assert np.array_equal(c.grid.h[d], cmodel.grid.h[d]), (sc_dir, d)
+            assert np.array_equal(c.ih[d].cpu().numpy(), 1.0 / cmodel.grid.h[d]), (sc_dir, d)
+        for k in ('eta_x', 'eta_y', 'eta_z', 'zeta'):
+            got = getattr(c, k).cpu().numpy()
+            want = getattr(cmodel, k).ravel('F')
+            assert got.dtype == want.dtype and got.shape == want.shape, (sc_dir, k)
+            assert relerr(got, want) < 1e-15, (sc_dir, k)
+        assert (c.eta_y is c.eta_x) == (cmodel.eta_y is cmodel.eta_x) == (case in ('isotropic', 'VTI')), sc_dir
+        assert (c.eta_z is c.eta_x) == (cmodel.eta_z is cmodel.eta_x) == (case in ('isotropic', 'HTI')), sc_dir
+        assert c.case == case and c.batch == lv.batch and c.flags == lv.flags
+        assert c.e.numel() == c.s.numel() == lv.batch * c.grid.n_edges
+    del levels, lv, c
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize('dtype', [complex, float])
+@pytest.mark.parametrize('shape,case,extras', TRANSFER_SHAPES, ids=map(_ids, TRANSFER_SHAPES))
+def test_device_restrict_and_prolong_vs_oracle_single_and_batched(shape, case, extras, dtype):
+    """DeviceLevel.restrict_to / prolong_from -- the path of a cycle: emg3d_dev_restrict_clear_batch and
+    emg3d_dev_prolong_batch with the weights and tables of child() packed into one upload each, source b of a batch
+    at b * n_edges -- for levels of 1, 2 and 5 right-hand sides and every admissible semicoarsening code, on five
+    sources with different random data (non-zero on all boundary edges):
+
+    * every source's coarse source equals mg_ref.restriction of ITS residual (1e-14), the coarse field, filled with a
+      sentinel before, is exactly zero, and the batched call gives each source the bits of its own batch-1 call;
+    * every source's fine field after `+=` equals mg_ref.prolongation (1e-14), its PEC edges keep their bits, the
+      coarse field is untouched, and batched equals single bit for bit."""
+    grid, vm, rng = random_level(shape, case, dtype, sum(shape) + 1, extras=extras, stretch=1.03)
+    dev = torch.device('cuda')
+    n = grid.n_edges
+    mask = pec_mask(grid)
+    levels = {batch: DeviceLevel.from_host(vm, dev, batch=batch) for batch in TRANSFER_BATCHES}
+    for sc_dir in admissible_sc_dirs(shape):
+        cgrid = coarse_grid(grid, sc_dir)
+        nc = cgrid.n_edges
+        res = [random_field(grid, dtype, rng) for _ in range(5)]
+        want_cs = [mg_ref.restriction(vm, r, r, sc_dir)[1].field for r in res]
+        ces = [random_field(cgrid, dtype, rng) for _ in range(5)]
+        fines = [random_field(grid, dtype, rng) for _ in range(5)]
+        want_f = []
+        for ce, f in zip(ces, fines):
+            ref = f.copy()
+            mg_ref.prolongation(ref, ce, sc_dir)
+            want_f.append(ref.field)
+        single_cs, single_f = {}, {}
+        for batch, lv in levels.items():
+            c = lv.child(sc_dir)['level']
+            assert c.batch == batch and c.grid.n_edges == nc and c.s.numel() == batch * nc
+            for srcs in _batch_calls(batch):
+                at = (shape, sc_dir, batch, srcs)
+                # restriction
+                lv.r.copy_(_stack(res, srcs))
+                c.s.fill_(_SENTINEL)
+                c.e.fill_(_SENTINEL)
+                assert lv.restrict_to(sc_dir) is c
+                cs = c.s.cpu().numpy().reshape(batch, nc)
+                assert not c.e.cpu().numpy().any(), at
+                assert np.array_equal(lv.r.cpu().numpy(), _stack(res, srcs).numpy()), at
+                for k, b in enumerate(srcs):
+                    d = relerr(cs[k], want_cs[b])
+                    assert d < 1e-14, (at, b, d)
+                    if batch == 1:
+                        single_cs[b] = cs[k].copy()
+                    else:
+                        assert np.array_equal(cs[k], single_cs[b]), (at, b)
+                # prolongation
+                c.e.copy_(_stack(ces, srcs))
+                lv.e.copy_(_stack(fines, srcs))
+                lv.prolong_from(sc_dir)
+                got = lv.e.cpu().numpy().reshape(batch, n)
+                assert np.array_equal(c.e.cpu().numpy(), _stack(ces, srcs).numpy()), at
+                for k, b in enumerate(srcs):
+                    d = relerr(got[k], want_f[b])
+                    assert d < 1e-14, (at, b, d)
+                    assert np.array_equal(got[k][mask], fines[b].field[mask]), (at, b)
+                    assert np.any(got[k][~mask] != fines[b].field[~mask]) or mask.all(), (at, b)
+                    if batch == 1:
+                        single_f[b] = got[k].copy()
+                    else:
+                        assert np.array_equal(got[k], single_f[b]), (at, b)
+    del levels, lv, c
+    torch.cuda.empty_cache()
+
+
+def _residual_checks(grid, vm, dtype, rng, levels, nsrc=5):
+    """residual / residual_sumsq / apply_A of the levels {batch: DeviceLevel} of one model against core.amat_x of the
+    oracle on nsrc sources with different random fields (non-zero on the boundary edges too); see
+    test_device_residual_operator_and_pec_vs_oracle_single_and_batched."""
+    n = grid.n_edges
+    es = [random_field(grid, dtype, rng) for _ in range(nsrc)]
+    ss = [random_field(grid, dtype, rng) for _ in range(nsrc)]
+    want = []
+    for e, s in zip(es, ss):
+        r = s.copy()
+        ocore.amat_x(r.fx, r.fy, r.fz, e.fx, e.fy, e.fz, vm.eta_x, vm.eta_y, vm.eta_z, vm.zeta, *grid.h)
+        want.append(r.field)
+    single_r, single_norm = {}, {}
+    for batch, lv in levels.items():
+        for srcs in _batch_calls(batch, nsrc):
+            at = (grid.shape_cells, batch, srcs)
+            x, b_ = _stack(es, srcs).to(lv.device), _stack(ss, srcs).to(lv.device)
+            lv.e.copy_(x)
+            lv.s.copy_(b_)
+            lv.r.fill_(_SENTINEL)
+            norms = np.atleast_1d(lv.residual(store=True, norm=True))
+            assert norms.shape == (batch,)
+            got = lv.r.cpu().numpy().reshape(batch, n)
+            for k, b in enumerate(srcs):
+                d = relerr(got[k], want[b])
+                assert d < 1e-13, (at, b, d)
+                assert norms[k] == pytest.approx(np.linalg.norm(want[b]), rel=1e-12), (at, b)
+                if batch == 1:
+                    single_r[b], single_norm[b] = got[k].copy(), norms[k]
+                else:
+                    # "a source must get the same bits whether it is solved alone or in a batch" (launch_residual)
+                    assert norms[k] == single_norm[b], (at, b, norms[k], single_norm[b])
+                    assert np.array_equal(got[k], single_r[b]), (at, b)
+            # store=False: the norm alone, r untouched
+            lv.r.fill_(_SENTINEL)
+            n2 = np.atleast_1d(lv.residual(store=False, norm=True))
+            assert torch.all(lv.r == _SENTINEL).item(), at
+            for k, b in enumerate(srcs):
+                assert n2[k] == pytest.approx(np.linalg.norm(want[b]), rel=1e-12), (at, b)
+            assert torch.equal(lv.e, x) and torch.equal(lv.s, b_), at
+            # residual_sumsq on other tensors (_level_on): the norm of copying them into e, s; e, s, r untouched
+            lv.e.fill_(_SENTINEL)
+            lv.s.fill_(-_SENTINEL)
+            sumsq = lv.residual_sumsq(x, b_)[:batch].cpu().numpy()
+            assert np.array_equal(np.sqrt(sumsq), norms), (at, np.sqrt(sumsq), norms)
+            assert torch.all(lv.e == _SENTINEL).item() and torch.all(lv.s == -_SENTINEL).item(), at
+            assert torch.all(lv.r == _SENTINEL).item(), at
+            # the Krylov operator on another tensor: A x = s - (s - A x)
+            out = torch.full_like(x, float('nan'))
+            assert lv.apply_A(x, out) is out
+            o = out.cpu().numpy().reshape(batch, n)
+            for k, b in enumerate(srcs):
+                d = relerr(o[k], ss[b].field - want[b])
+                assert d < 1e-12, (at, b, d)
+            assert np.array_equal(x.cpu().numpy(), _stack(es, srcs).numpy()), at
+            assert torch.all(lv.e == _SENTINEL).item() and torch.all(lv.r == _SENTINEL).item(), at
+
+
+@pytest.mark.parametrize('dtype', [complex, float])
+@pytest.mark.parametrize('shape,case,extras', TRANSFER_SHAPES + ODD_SHAPES, ids=map(_ids, TRANSFER_SHAPES + ODD_SHAPES))
+def test_device_residual_operator_and_pec_vs_oracle_single_and_batched(shape, case, extras, dtype):
+    """DeviceLevel.residual / residual_sumsq / apply_A / pec_zero (k_residual + k_reduce_sum, k_apply_operator,
+    k_pec_zero) on levels of 1, 2 and 5 right-hand sides, five sources with different random fields and sources:
+
+    * residual(store=True, norm=True): values against core.amat_x of the oracle per source (1e-13), one norm per
+      source against the l2-norm of the oracle's residual (1e-12), batched values and norms bit-identical to the
+      single-source ones (per-source partial sums [b nblk, (b+1) nblk), one k_reduce_sum workgroup per source);
+    * store=False leaves r (a sentinel) alone;
+    * residual_sumsq(x, b) on other tensors gives exactly the norm of copying them into e, s, and touches none of
+      e, s, r;
+    * apply_A(x, out) against s - residual of the oracle (1e-12);
+    * pec_zero on ones: exactly the tangential boundary edges of every right-hand side become zero."""
+    grid, vm, rng = random_level(shape, case, dtype, sum(shape) + 2, extras=extras, stretch=1.03)
+    dev = torch.device('cuda')
+    n = grid.n_edges
+    levels = {batch: DeviceLevel.from_host(vm, dev, batch=batch) for batch in TRANSFER_BATCHES}
+    _residual_checks(grid, vm, dtype, rng, levels)
+    mask = pec_mask(grid)
+    assert 0 < mask.sum() < n
+    for batch, lv in levels.items():
+        lv.e.fill_(1.0)
+        lv.s.fill_(1.0)
+        lv.pec_zero()
+        got = lv.e.cpu().numpy().reshape(batch, n)
+        for k in range(batch):
+            assert np.array_equal(got[k] == 0, mask), (shape, batch, k)
+            assert np.all(got[k][~mask] == 1), (shape, batch, k)
+        assert torch.all(lv.s == 1.0).item()
+    del levels, lv
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize('dtype', [complex, float])
+@pytest.mark.parametrize('roll', [1, 0])
+def test_blocked_residual_with_ragged_last_blocks_vs_oracle(roll, dtype):
+    """The residual and operator kernels with several planes per workgroup (option residual_zb; launch_residual and
+    emg3d_dev_apply_operator take that path only where grid.x * grid.y * (planes / residual_zb) >= 8 x compute
+    units -- asserted here from the device's CU count, so the case cannot fall back to one plane unnoticed) on a
+    grid whose last x-block (131 = 2 x 64 + 3 nodes), last y-block (259 = 64 x 4 + 3) and last plane block (35 = 11
+    x 3 + 2) are partly empty: with the column walk that carries operands between planes (residual_roll = 1,
+    k_residual<T, true>) and cell by cell (0): values 1e-13, norms 1e-12 against the oracle, 1 and 2 right-hand
+    sides, batched bit-identical to single."""
+    shape, zb = (130, 258, 34), 3
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    gx, gy, planes = -(-(shape[0] + 1) // 64), -(-(shape[1] + 1) // 4), shape[2] + 1
+    assert gx * gy * (planes // zb) >= 8 * cus, (gx, gy, planes, cus)
+    assert (shape[0] + 1) % 64 and (shape[1] + 1) % 4 and planes % zb
+    grid, vm, rng = random_level(shape, 'triaxial', dtype, 77 + roll, stretch=1.03)
+    dev = torch.device('cuda')
+    lib = _lib.lib()
+    before = (lib.emg3d_get_option(b'residual_zb'), lib.emg3d_get_option(b'residual_roll'))
+    try:
+        assert lib.emg3d_set_option(b'residual_zb', zb) == 0 and lib.emg3d_set_option(b'residual_roll', roll) == 0
+        assert (lib.emg3d_get_option(b'residual_zb'), lib.emg3d_get_option(b'residual_roll')) == (zb, roll)
+        levels = {batch: DeviceLevel.from_host(vm, dev, batch=batch) for batch in (1, 2)}
+        _residual_checks(grid, vm, dtype, rng, levels, nsrc=2)
+    finally:
+        lib.emg3d_set_option(b'residual_zb', before[0])
+        lib.emg3d_set_option(b'residual_roll', before[1])
+    assert (lib.emg3d_get_option(b'residual_zb'), lib.emg3d_get_option(b'residual_roll')) == before
+    del levels
+    torch.cuda.empty_cache()

@@ -12,7 +12,8 @@ import pytest
 from oracle import core as ocore
 from oracle import mg_ref
 from emu import emu
-from helpers import relerr
+from helpers import (admissible_sc_dirs, coarse_grid, pec_mask, random_field, random_level, relerr,
+                     sc_factors)
 
 LR = {'gauss_seidel': 0, 'gauss_seidel_x': 1, 'gauss_seidel_y': 2, 'gauss_seidel_z': 3}
 
@@ -445,3 +446,115 @@ def test_wide_line_form_matches_oracle(shape, freq):
             assert relerr(b.field, a.field) < tol, (shape, fn)
     finally:
         emu.lib().emu_set_line_wide(0)
+
+
+# --- grid transfer, model restriction and residual bodies beyond one workgroup ---------------------------------------
+_TRANSFER_SIZES = [2, 3, 4, 5, 6, 10, 18, 34, 66, 70, 130]
+_ANISOTROPY = ('isotropic', 'VTI', 'HTI', 'triaxial')
+
+
+def _transfer_case(seed):
+    """(shape, anisotropy case, dtype, extras) of seeded case `seed`: every direction drawn from _TRANSFER_SIZES
+    (1, 2 and 3 blocks of 64 nodes in x, up to 33 rows of 4 in y; odd counts, 2-cell directions), the largest
+    direction stepped down while the grid has more than 1.5e5 cells."""
+    rng = np.random.default_rng(4000 + seed)
+    shape = [int(rng.choice(_TRANSFER_SIZES)) for _ in range(3)]
+    while np.prod(shape) > 150000:
+        i = int(np.argmax(shape))
+        shape[i] = _TRANSFER_SIZES[_TRANSFER_SIZES.index(shape[i]) - 1]
+    return tuple(shape), _ANISOTROPY[seed % 4], (complex, float)[(seed // 4) % 2], seed % 3 == 2
+
+
+_TRANSFER_SEEDS = range(20)
+
+
+def test_transfer_cases_cover_every_semicoarsening_code():
+    """Over the parametrisation of test_transfer_and_residual_bodies_match_oracle_at_many_shapes: each of the
+    seven semicoarsening codes is admissible at least three times, odd directions occur (and are then never
+    coarsened), grids reach beyond one 64 x 4 block in x and y, both dtypes and all four anisotropy cases occur,
+    with and without epsilon_r / mu_r."""
+    count = np.zeros(7, dtype=int)
+    cases = [_transfer_case(seed) for seed in _TRANSFER_SEEDS]
+    for shape, _, _, _ in cases:
+        for sc_dir in admissible_sc_dirs(shape):
+            count[sc_dir] += 1
+            assert all(f == 1 or n % 2 == 0 for f, n in zip(sc_factors(sc_dir), shape))
+    assert np.all(count >= 3), count
+    assert sum(any(n % 2 for n in shape) for shape, _, _, _ in cases) >= 3
+    assert sum(shape[0] + 1 > 128 for shape, _, _, _ in cases) >= 2          # three blocks in x
+    assert sum(64 < shape[0] + 1 <= 128 for shape, _, _, _ in cases) >= 2    # two blocks in x
+    assert {c for _, c, _, _ in cases} == set(_ANISOTROPY)
+    assert {(d, x) for _, _, d, x in cases} == {(complex, False), (complex, True), (float, False), (float, True)}
+
+
+@pytest.mark.parametrize('seed', _TRANSFER_SEEDS, ids=lambda s: 'x'.join(map(str, _transfer_case(s)[0])))
+def test_transfer_and_residual_bodies_match_oracle_at_many_shapes(seed):
+    """restrict_node, restrict_param_cell, prolong_cell, residual_cell and residual_column (stencil.h), walked over
+    their launch grids on the CPU, against the oracle (mg_ref.restriction / restrict_model_parameters /
+    prolongation, core.amat_x) on seeded random grids of up to 130 cells per direction: several blocks of 64 x 4
+    threads, interior nodes away from every boundary, ragged last blocks, stretched widths, all anisotropy cases,
+    complex and real, with and without epsilon_r / mu_r -- for every semicoarsening code that coarsens even
+    directions only. Tolerances: 1e-14 rel-L2 transfers, 1e-15 model sums, 1e-13 residual values and squared norm
+    (those of the golden-vector tests above)."""
+    shape, case, dtype, extras = _transfer_case(seed)
+    grid, vm, rng = random_level(shape, case, dtype, 100 + seed, extras=extras)
+    if extras and dtype is complex:
+        assert np.abs(vm.eta_x.real / vm.eta_x.imag).max() > 1e-2         # eta has a real part that matters
+    if extras:
+        assert not np.array_equal(vm.zeta, grid.cell_volumes.reshape(shape, order='F'))
+    mask = pec_mask(grid)
+
+    # residual: stored, in place (r aliases s), norm only, and the column walk
+    e, s = random_field(grid, dtype, rng), random_field(grid, dtype, rng)
+    want = s.copy()
+    ocore.amat_x(want.fx, want.fy, want.fz, e.fx, e.fy, e.fz, vm.eta_x, vm.eta_y, vm.eta_z, vm.zeta, *grid.h)
+    wss = np.linalg.norm(want.field) ** 2
+    r = mg_ref.Field(grid, dtype=dtype)
+    ss = emu.residual(e, s, vm, r)
+    assert relerr(r.field, want.field) < 1e-13
+    assert abs(ss / wss - 1) < 1e-13
+    s2 = s.copy()
+    assert abs(emu.residual(e, s2, vm, s2) / wss - 1) < 1e-13
+    assert relerr(s2.field, want.field) < 1e-13
+    e_in, s_in = e.field.copy(), s.field.copy()
+    assert abs(emu.residual(e, s, vm) / wss - 1) < 1e-13
+    for zb in (1, 3, 8):
+        rc = mg_ref.Field(grid, dtype=dtype)
+        rc.field[:] = np.nan
+        ssc = emu.residual_column(e, s, vm, rc, zb)
+        assert relerr(rc.field, want.field) < 1e-13, zb
+        assert abs(ssc / wss - 1) < 1e-13, zb
+    assert np.array_equal(e.field, e_in) and np.array_equal(s.field, s_in)
+
+    for sc_dir in admissible_sc_dirs(shape):
+        cgrid = coarse_grid(grid, sc_dir)
+        # restriction of a residual that is non-zero on the boundary edges too (read with clamped indices)
+        res = random_field(grid, dtype, rng)
+        cmodel, cs, _ = mg_ref.restriction(vm, res, res, sc_dir)
+        assert cmodel.grid.shape_cells == cgrid.shape_cells
+        w9 = []
+        for f, w3 in zip(sc_factors(sc_dir), mg_ref.restriction_weights(grid, cgrid, sc_dir)):
+            w9 += [np.ascontiguousarray(w, dtype=np.float64) if f == 2 else None for w in w3]
+        c = mg_ref.Field(cgrid, dtype=dtype)
+        c.field[:] = np.nan
+        emu.restrict(c, res, w9, shape, sc_dir)
+        assert relerr(c.field, cs.field) < 1e-14, sc_dir
+        # model sums
+        for k in ('eta_x', 'eta_y', 'eta_z', 'zeta'):
+            got = emu.restrict_param(getattr(vm, k), sc_dir)
+            ref = mg_ref.restrict_model_parameters(getattr(vm, k), sc_dir)
+            assert got.shape == ref.shape
+            assert relerr(got, ref) < 1e-15, (sc_dir, k)
+            assert relerr(got, getattr(cmodel, k)) < 1e-15, (sc_dir, k)
+        # prolongation (+=) of a coarse field with non-zero boundary values onto a non-zero fine field
+        ce = random_field(cgrid, dtype, rng)
+        fine = random_field(grid, dtype, rng)
+        before = fine.field.copy()
+        ref = fine.copy()
+        mg_ref.prolongation(ref, ce, sc_dir)
+        il, w = prolong_tables(cgrid, grid)
+        emu.prolong(fine, ce, il, w, shape, sc_dir)
+        assert relerr(fine.field, ref.field) < 1e-14, sc_dir
+        assert relerr(fine.field - before, ref.field - before) < 1e-14, sc_dir      # the correction itself
+        assert np.array_equal(fine.field[mask], before[mask]), sc_dir             # PEC edges: bit-unchanged
+        assert np.any(fine.field[~mask] != before[~mask]) or mask.all()
