@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -72,27 +73,19 @@ int g_point_slab = 0;
 // include/emg3d_amd.h), so it is part of the algorithm, not a free tuning knob: the
 // oracle applies the same rule. <= 0 never, 1 always.
 int g_point_tile_min = 1 << 20;
-// Line smoothers: 0 = three launches per colour (rhs, forward, backward), 1 = one fused
-// launch per colour, 2 = fused when the colour class has at most g_line_fuse_max lines.
-// Fused is faster at every size measured (256^3: 8.4-9.0 against 9.5-10.0 ms per two sweeps).
+// Line smoothers: 0 = three launches per colour (rhs, forward, backward), non-zero = one fused
+// launch per colour. Fused is faster at every size measured (256^3: 8.4-9.0 against 9.5-10.0 ms per two sweeps).
 int g_line_fuse = 2;
-int g_line_fuse_max = 1 << 30;
-// fused line kernel: keep the right-hand-side / solution records of a workgroup's lines in
-// LDS when they fit into this many bytes (0 = never)
 // skip the colour pass that repeats the previous sweep's last one (bit-identical results)
 int g_skip_repeat = 1;
 // tiled point smoother: the tiles where two consecutive sweeps meet run both on one LDS copy
 int g_tile_fuse = 1;
+// fused line kernel: keep the right-hand-side / solution records of a workgroup's lines in LDS when they fit (0 = never)
 int g_line_lds = 1;
-// tiled point smoother: software prefetch of the next colour step's inputs (0 none, 1 source, 2 source + eta sums)
-int g_point_prefetch = 0;
 // residual kernel: planes a workgroup walks on large levels (1 = one plane per workgroup)
 int g_residual_zb = 8;
 // ... and carries the operands a cell shares with the cell below it in registers (1, default; 0: every cell loads all of its own)
 int g_residual_roll = 1;
-// fused line kernel with the records in the global scratch (the largest levels): the instantiation
-// that is held to 256 registers, so that two workgroups share a CU and overlap their phases
-int g_line_occ2 = 0;
 // point smoother: levels with at most this many interior nodes run all passes of a call in one
 // single-workgroup launch (k_gs_point_small); 0: off
 int g_point_small = 512;
@@ -116,9 +109,6 @@ int g_line_stream_r = 0;           // rows per chunk of the ring (0: 16)
 // the global scratch and whose lines have at least this many blocks run k_line_stream -- groups of up
 // to four right-hand sides per workgroup, the factors fetched once per group (<= 0: never)
 int g_line_stream_bmin = 64;
-// one source: the coupling entries of a block (8 reals) recomputed by the producer waves from zeta / h and handed
-// to the chain waves through a second LDS ring instead of being fetched from the lfac records (1, default; 0: fetched)
-int g_line_stream_lf = 1;
 // the wide form of the line pass (k_line_wide: four-unknown chains on sixteen lanes per half-line, one thread per
 // block for everything else) on lines of at most this many blocks, where the level holds the N records (launch.h:
 // line_wide_capable -- a function of the level's shape alone, so that buffers sized once stay valid whatever the
@@ -130,28 +120,12 @@ int g_line_wide = 33;
 // then one workgroup per CU: 21.1 -> 17.3 us per launch at 256 x 32 x 32, k_line_colour 20.4; on shorter lines the fifth
 // wave only adds to the barriers: 5.8 -> 6.5 us); 192 / 256: forced
 int g_line_wide_bt = 0;
-// TIMING EXPERIMENTS ONLY (wrong results): bit 0: the records of all blocks of a line alias one row of
-// the global scratch -- what the level-0 pass would cost if its right-hand-side / solution records
-// never left the chip
-int g_line_debug = 0;
-// COMPACT line factors (k_line_stream): the T records and the w records of the streamed colour passes stored in
-// single precision (120 + 2 x 40 instead of 240 + 2 x 80 B per block and pass; every operation in fp64). 0 (default):
-// where the level asks for it (emg3d_level::flags & EMG3D_LEVEL_LINE_COMPACT -- the caller's promise that the level
-// solves a correction equation, include/emg3d_amd.h); 1: on every level whose direction streams (timing / tests);
-// -1: never
+// COMPACT line factors: the T records of the colour passes on lines of more than LINE_SHORT blocks, and the w records of
+// the streamed ones, stored in single precision (k_line_stream: 120 + 2 x 40 instead of 240 + 2 x 80 B per block and
+// pass; every operation in fp64). 0 (default): where the level asks for it (emg3d_level::flags &
+// EMG3D_LEVEL_LINE_COMPACT -- the caller's promise that the level solves a correction equation, include/emg3d_amd.h);
+// 1: on every level whose kernels can read them (line_compact_used; timing / tests); -1: never
 int g_line_compact = 0;
-// ... depth of the chain waves' factor prefetch ring in the compact kernel (4 or 8 block steps ahead: a compact ring
-// entry holds 12 instead of 24 registers). 0 (default): 8 for x-lines, 4 for y- and z-lines -- same-box A/B at 256^3,
-// ms per launch x / y / z: fp64 records 0.885 / 0.955 / 0.969, compact with 4: 0.817 / 0.757 / 0.748, with 8: 0.740 /
-// 0.794 / 0.789 (the producers of y / z lines, whose gathers use half of every cache line, are what the chains wait
-// for: more chain loads in flight delay them; x-line producers read whole lines)
-int g_line_compact_rd = 0;
-// (Measured and not kept as options -- profiles/r06_compact_line_kernel_ab.txt: two workgroups of four waves per CU with 8
-// rows per chunk, 0.915 / 0.761 / 0.773 ms per launch against 0.817 / 0.757 / 0.748; four producer waves instead of six,
-// 0.732 / 0.780 / 0.770 against 0.697 / 0.766 / 0.764; the w records of the rows nearest the middle block in LDS, +4-10 %.)
-// ... also on the levels that run k_line_colour with lines of more than LINE_SHORT blocks (1, default; 0: streamed levels only)
-int g_line_compact_colour = 1;
-constexpr int LS_PROD_COMPACT = 384;      // producer threads of the compact single-source kernel: six waves
 
 // eta edge sums of the tiled point smoother: 8-byte storage (launch.h: tile_pst_*) for real
 // fields and for complex fields whose eta are purely imaginary (emg3d_level::flags)
@@ -254,22 +228,19 @@ template <class T> __global__ __launch_bounds__(256) void k_point_setup(emg::Lev
     if (ix <= L.nx && iy <= L.ny) emg::point_setup_cell<T>(L, pst, ix, iy, blockIdx.z);
 }
 
-// workgroup barrier that orders LDS traffic only: global loads issued before it (the
-// prefetch of the next node's inputs) stay in flight across it
+// workgroup barrier that orders LDS traffic only: global loads issued before it stay in flight across it
 __device__ __forceinline__ void lds_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 // Point smoother, tiled schedule (launch.h): one workgroup = one tile of one tile colour;
-// the tile's edges live in LDS while the four node colours run on it. The model/source
-// inputs of the next colour's node are fetched while the current node is solved.
-// ST: where the eta edge sums come from: 0 formed on the fly from eta; 2 tile-major buffer of
-// k_point_setup_tile, full values; 3 the same, stored halves (8 bytes: launch.h tile_pst_*).
-// PF: software prefetch -- the global inputs (source; PF = 2: eta sums too) of the NEXT colour
-// step are requested before the current node is solved, so their latency overlaps the ~600
-// fp64 instructions of the 6x6 solve inside the wave, not only across waves.
-template <class T, class TB, int ST, bool BATCH, int PFV>
+// the tile's edges live in LDS while the four node colours run on it. Every colour step fetches
+// the model / source inputs of its own node; what hides their latency is the second workgroup
+// of the CU (software prefetch of the next step's inputs was measured and not adopted: DESIGN.md 4.2).
+// ST: where the eta edge sums come from: 0 formed on the fly from eta; otherwise the tile-major buffer
+// of k_point_setup_tile in storage mode ST (launch.h: PST_*, tile_pst_*).
+template <class T, class TB, int ST, bool BATCH>
 __global__ __launch_bounds__(TB::THREADS, 2) void k_gs_point_tile(emg::Level<T> L, const void *pst, emg::TilePair P,
                                                                   int colours, int nsteps)
 {
@@ -298,71 +269,24 @@ __global__ __launch_bounds__(TB::THREADS, 2) void k_gs_point_tile(emg::Level<T> 
         colour = (colours >> (2 * cc)) & 3;
         return emg::tile_node<TB>(L.nx, L.ny, L.nz, x0, y0, z0, colour, t, ix, iy, iz);
     };
-    auto load_eta = [&](int ix, int iy, int iz, int colour, emg::PointIn<T> &in) {
-        if (ST == 0) emg::point_load_eta<T, false>(L, nullptr, ix, iy, iz, in);
-        else emg::tile_pst_load<T, TB, ST>(pst, ntx, nty, tx, ty, tz, colour, t, in);
-    };
-    // PFV = 3: paired source loads. A thread's four nodes (one per node colour) are the 2 x 2
-    // patch (x0 + 2 jx + {0,1}, y0 + 2 jy + {0,1}) of its plane; the two nodes of a row differ
-    // in the low colour bit. Fetched per node, the source values of a row are stride-2 gathers
-    // that touch every cache line of the row in BOTH steps. Here the first of the two steps
-    // fetches the values of both nodes (same lines, same instruction stream) and holds the
-    // partner's six values (24 registers per row) until its step comes.
-    constexpr bool PAIR = PFV == 3;
-    constexpr int PF = PAIR ? 0 : PFV;
-    T held_lo[6], held_hi[6];                  // partner values of the row with colour bit 1 = 0 / 1
-    int held_lo_c = -1, held_hi_c = -1;        // the colour they belong to (-1: none)
-    auto pair_source = [&](int ix, int iy, int iz, int colour, bool ok, T (&held)[6], int &held_c, emg::PointIn<T> &in) {
-        if (held_c == colour) {
-#pragma unroll
-            for (int r = 0; r < 6; ++r) in.s[r] = held[r];
-            held_c = -1;
-            return;
-        }
-        emg::point_load_source<T>(L, ix, iy, iz, in);
-        int px, py, pz;
-        const bool pok = emg::tile_node<TB>(L.nx, L.ny, L.nz, x0, y0, z0, colour ^ 1, t, px, py, pz);
-        if (!pok) { px = ix; py = iy; pz = iz; }
-        (void)ok;
-        emg::PointIn<T> q;
-        emg::point_load_source<T>(L, px, py, pz, q);
-#pragma unroll
-        for (int r = 0; r < 6; ++r) held[r] = q.s[r];
-        held_c = colour ^ 1;
-    };
     emg::PointIn<T> in;
     int ix, iy, iz, colour;
     bool ok = node(0, ix, iy, iz, colour);
-    if (PF >= 1) emg::point_load_source<T>(L, ix, iy, iz, in);      // issued ahead of the tile copy
-    if (PF >= 2) load_eta(ix, iy, iz, colour, in);
     emg::tile_load<T, TB>(L, lds, x0, y0, z0, t);
     lds_barrier();
     // two workgroups per CU (launch bounds: <= 256 registers, 2 x 79 KB of LDS): while one
-    // waits for the inputs of its next node, the other one computes
+    // waits for the inputs of its node, the other one computes
 #pragma unroll 1
     for (int cc = 0; cc < nsteps; ++cc) {     // node colours, two bits each (4, or 7-8 for two fused sweeps)
-        if (PAIR) {
-            if (colour & 2) pair_source(ix, iy, iz, colour, ok, held_hi, held_hi_c, in);
-            else pair_source(ix, iy, iz, colour, ok, held_lo, held_lo_c, in);
-        } else if (PF < 1) emg::point_load_source<T>(L, ix, iy, iz, in);
-        if (PF < 2) load_eta(ix, iy, iz, colour, in);
+        emg::point_load_source<T>(L, ix, iy, iz, in);
+        if (ST == 0) emg::point_load_eta<T, false>(L, nullptr, ix, iy, iz, in);
+        else emg::tile_pst_load<T, TB, ST>(pst, ntx, nty, tx, ty, tz, colour, t, in);
         emg::point_load_zeta<T>(emg::ZetaTile<E>{ed}, ix, iy, iz, in);
-        // the next step's node and its global inputs (the last step asks for its own again)
-        emg::PointIn<T> nxt;
+        // the next step's node (the last step asks for its own again)
         int jx, jy, jz, ncol;
         const bool nok = node(min(cc + 1, nsteps - 1), jx, jy, jz, ncol);
-        if (PF >= 1) emg::point_load_source<T>(L, jx, jy, jz, nxt);
-        if (PF >= 2) load_eta(jx, jy, jz, ncol, nxt);
         if (ok) emg::point_update<T, E>(L, in, ed, ix, iy, iz);
         lds_barrier();
-        if (PF >= 1) {
-#pragma unroll
-            for (int r = 0; r < 6; ++r) in.s[r] = nxt.s[r];
-        }
-        if (PF >= 2) {
-#pragma unroll
-            for (int r = 0; r < 6; ++r) in.st[r] = nxt.st[r];
-        }
         ix = jx; iy = jy; iz = jz; colour = ncol; ok = nok;
     }
     emg::tile_store<T, TB>(L, lds, x0, y0, z0, t);
@@ -561,19 +485,10 @@ template <class T, class FT = T> struct QuadRow {
 #pragma unroll
         for (int r = 0; r < 5; ++r) t[r] = *reinterpret_cast<const FT *>(f + a.ft[r]);
         t44 = *reinterpret_cast<const FT *>(f + a.ft[5]);
-        if constexpr (!RECS) {
-        } else if constexpr (A::split) {
-            // split records: the slot is in LDS or in the global scratch, depending on the row --
-            // both are read (the one that does not apply at a fixed valid address), no branch
-            const bool in = a.in_lds(k);
-            const T *const pl = in ? a.pvj(k) : a.ldum;
-            const T *const pg = in ? a.gdum : a.gpvj(k);
-            const T vl = *pl, vg = *pg;
-            v = in ? vl : vg;
-        } else {
+        if constexpr (RECS) {
             v = *a.pvj(k);
+            v4 = *a.pv4(k);
         }
-        if constexpr (RECS) v4 = *a.pv4(k);
         if constexpr (LF) {
             bA = *reinterpret_cast<const double *>(lf + a.la);
             bD = *reinterpret_cast<const double *>(lf + a.ld);
@@ -622,12 +537,6 @@ template <class T> struct VecRef {
     int stride, line0, width;
     T *base4;
     int stride4, line04;
-    // split records (fused kernel, VMODE 3): rows klo <= k < khi keep their slots 0..3 in LDS
-    // (`base`, shifted by -klo rows, width 4), all other rows in the global scratch (`gbase`, laid
-    // out like VecRef::global); slot 4 of every row is in the global scratch
-    T *gbase;
-    int gstride, klo, khi;
-    __device__ __forceinline__ T *pg(int k, int line, int r) const { return gbase + ((size_t)k * gstride + line) * 5 + r; }
     __device__ __forceinline__ T *p(int k, int line, int r) const
     {
         return base + ((size_t)k * stride + (line - line0)) * width + r;
@@ -638,7 +547,7 @@ template <class T> struct VecRef {
     }
     static __device__ __forceinline__ VecRef global(T *vec, int nlines)
     {
-        return VecRef{vec, nlines, 0, 5, vec, nlines, 0, vec, nlines, 0, 0};
+        return VecRef{vec, nlines, 0, 5, vec, nlines, 0};
     }
 };
 // Addresses of one lane inside the half-chain loops, split into a per-block part that is
@@ -647,8 +556,7 @@ template <class T> struct VecRef {
 // step pays 64-bit per-lane multiplies (v_mad_u64_u32: quarter rate) -- a quarter of the
 // issue slots of a step.
 // FT / WT: storage types of the T records / of the right-hand-side and w records (T, or emg::compact_of<T>)
-template <class T, int HALF, bool SPLIT = false, class FT = T, class WT = T> struct LaneAddr {
-    static constexpr bool split = SPLIT;
+template <class T, int HALF, class FT = T, class WT = T> struct LaneAddr {
     using fac_t = FT;
     const char *fac, *lfac;      // uniform
     size_t frow, lrow;           // bytes of one block row of the factor arrays (all lines)
@@ -657,13 +565,6 @@ template <class T, int HALF, bool SPLIT = false, class FT = T, class WT = T> str
     char *vb, *vb4;              // uniform bases of the vec slots 0..3 / slot 4
     size_t vrow, vrow4;          // bytes of one block row of the records
     unsigned vj, v4;             // lane byte offsets of slot j / slot 4
-    // SPLIT: the global home of slots 0..3, the row range held in LDS, this lane's row offset, and
-    // the fixed addresses read when a slot lives in the other space
-    char *gvb;
-    size_t gvrow;
-    unsigned gvj;
-    int klo, khi, radd;
-    const WT *ldum, *gdum;
     __device__ __forceinline__ LaneAddr(const FT *f, const double *lf, int nlines, int line, int j, const VecRef<WT> &V)
     {
         fac = reinterpret_cast<const char *>(f);
@@ -690,25 +591,6 @@ template <class T, int HALF, bool SPLIT = false, class FT = T, class WT = T> str
         vrow4 = (size_t)V.stride4 * 5 * sizeof(WT);
         vj = (unsigned)(((line - V.line0) * V.width + j) * sizeof(WT)) + ((HALF && j == 0) ? (unsigned)vrow : 0u);
         v4 = (unsigned)(((line - V.line04) * 5 + 4) * sizeof(WT));
-        if (SPLIT) {
-            gvb = reinterpret_cast<char *>(V.gbase);
-            gvrow = (size_t)V.gstride * 5 * sizeof(WT);
-            gvj = (unsigned)((line * 5 + j) * sizeof(WT));
-            klo = V.klo; khi = V.khi;
-            radd = (HALF && j == 0) ? 1 : 0;
-            ldum = reinterpret_cast<const WT *>(vb + (size_t)V.klo * vrow + (unsigned)(((line - V.line0) * V.width + j) * sizeof(WT)));
-            gdum = reinterpret_cast<const WT *>(gvb + gvj);
-        }
-    }
-    // SPLIT: is this lane's slot of block k (record row k, or k-1 (+1 for lane 0) in a mirrored half) in LDS?
-    __device__ __forceinline__ bool in_lds(int k) const
-    {
-        const int row = (HALF ? k - 1 : k) + radd;
-        return row >= klo && row < khi;
-    }
-    __device__ __forceinline__ WT *gpvj(int k) const
-    {
-        return reinterpret_cast<WT *>(gvb + (size_t)((HALF ? k - 1 : k) + radd) * gvrow + gvj);
     }
     __device__ __forceinline__ WT *pvj(int k) const
     {
@@ -746,7 +628,7 @@ __device__ __forceinline__ void quad_forward_step(const Q &q, const T v, const T
     w4p = w4;
 }
 
-template <class T, int HALF, int QD, bool SPLIT = false, class FT = T>
+template <class T, int HALF, int QD, class FT = T>
 __device__ __forceinline__ void quad_forward(int n0, int n0p, int nlines, int qline, int qend, int j, const FT *fac,
                                              const double *lfac, const VecRef<T> V, T *dummy, T *dummy4)
 {
@@ -759,7 +641,7 @@ __device__ __forceinline__ void quad_forward(int n0, int n0p, int nlines, int ql
     T *const dslot = dummy + ((threadIdx.x & 63) >> 2) * 5;
     T *const dslot4 = dummy4 + ((threadIdx.x & 63) >> 2) * 5;
     QuadRow<T, FT> ring[QD];
-    const LaneAddr<T, HALF, SPLIT, FT, T> LA(fac, lfac, nlines, line, j, V);
+    const LaneAddr<T, HALF, FT, T> LA(fac, lfac, nlines, line, j, V);
     auto fetch = [&](QuadRow<T, FT> &q, int i) { q.load(LA, W.fwd(W.clampi(i))); };
 #pragma unroll
     for (int d = 0; d < QD; ++d) fetch(ring[d], d);
@@ -777,17 +659,8 @@ __device__ __forceinline__ void quad_forward(int n0, int n0p, int nlines, int ql
             T wn, w4;
             quad_forward_step(q, q.v, q.v4, nz, is0, wsel, w4p, wn, w4);
             T *const o4 = active ? LA.pv4(k) : dslot4 + 4;
-            if constexpr (SPLIT) {
-                // (dummy: LDS, dummy4: global -- one store into either space, the idle one to its dummy slot)
-                const bool in = LA.in_lds(k);
-                T *const ol = (active && in) ? LA.pvj(k) : dslot + j;
-                T *const og = (active && !in) ? LA.gpvj(k) : dslot4 + j;
-                *ol = wn;
-                *og = wn;
-            } else {
-                T *const oj = active ? LA.pvj(k) : dslot + j;
-                *oj = wn;
-            }
+            T *const oj = active ? LA.pvj(k) : dslot + j;
+            *oj = wn;
             *o4 = w4;
             fetch(ring[d], i0 + d + QD);
         }
@@ -870,7 +743,7 @@ __device__ __forceinline__ void quad_middle(int n0, int n0p, int nlines, int lin
 // and the ring's 160 are then not live together: the batched kernel must stay under 256
 // registers so that two workgroups share a CU); otherwise the ring fetch is in flight while
 // the middle block is solved.
-template <class T, int DIR, int HALF, int QD, bool MIDFIRST = false, bool SPLIT = false, class FT = T>
+template <class T, int DIR, int HALF, int QD, bool MIDFIRST = false, class FT = T>
 __device__ __forceinline__ void quad_backward(const emg::Level<T> &L, int colour, int cntp, int cntq, int n0p,
                                               int qline, int qend, int j, const FT *fac, const double *lfac,
                                               const VecRef<T> V, T *dummy, size_t boff = 0)
@@ -896,7 +769,7 @@ __device__ __forceinline__ void quad_backward(const emg::Level<T> &L, int colour
     T *const dj = dslot + j, *const d4 = dslot + 4;
 
     QuadRow<T, FT> ring[QD];
-    const LaneAddr<T, HALF, SPLIT, FT, T> LA(fac, lfac, nlines, line, j, V);
+    const LaneAddr<T, HALF, FT, T> LA(fac, lfac, nlines, line, j, V);
     auto fetch = [&](QuadRow<T, FT> &q, int i) {
         q.load(LA, min(max(W.bwd(W.clampi(i)), HALF), n0p - 1));   // a half without blocks still prefetches
     };
@@ -1038,16 +911,8 @@ __global__ __launch_bounds__(LC_THREADS, BATCH ? 2 : 1) void k_line_colour(emg::
         V = VecRef<T>{lvec, lpw, line0, 4, vec, nlines, 0};
         dum = lvec + (size_t)lpw * n0p * 4;
         dum4 = dummy;
-    } else if (VMODE == 3) {
-        // lines too long for mode 2: the rows around the middle block in LDS, the outer rows in the
-        // global scratch (launch.h: line_split_rows)
-        const emg::LineSplit sp = emg::line_split_rows(A.n0(), n0p, lpw, sizeof(T));
-        V = VecRef<T>{lvec - (size_t)sp.klo * lpw * 4, lpw, line0, 4, vec, nlines, 0, vec, nlines, sp.klo, sp.khi};
-        dum = lvec + (size_t)lpw * (sp.khi - sp.klo) * 4;
-        dum4 = dummy;
     } else {
-        // (vstride == ~0 in a single-source launch: the debug aliasing of option line_debug)
-        V = VecRef<T>::global(vec, (!BATCH && vstride == ~(size_t)0) ? 0 : nlines);
+        V = VecRef<T>::global(vec, nlines);
         dum = dum4 = dummy;
     }
     // (1) right-hand sides of the workgroup's lines; x-lines run the lanes along the line. Only the n0 real blocks
@@ -1063,25 +928,15 @@ __global__ __launch_bounds__(LC_THREADS, BATCH ? 2 : 1) void k_line_colour(emg::
         emg::line_of_thread<DIR>(colour, cntp, cntq, lid % cntp, lid / cntp, i1, i2, l2);
         T rhs[5];
         emg::line_rhs<T, DIR>(A, k, i1, i2, rhs);
-        if (VMODE == 3 && (k < V.klo || k >= V.khi)) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) *V.pg(k, lid, r) = rhs[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) *V.p(k, lid, r) = rhs[r];
-        }
+        for (int r = 0; r < 4; ++r) *V.p(k, lid, r) = rhs[r];
         *V.p4(k, lid) = rhs[4];
     }
     // identity padding blocks behind block n0 - 1: rhs = 0 (dealt from the last thread downwards: the helper waves)
     for (int i = LC_THREADS - 1 - (int)threadIdx.x; i < nl * (n0p - n0r); i += LC_THREADS) {
         const int k = n0r + i / nl, lid = line0 + i % nl;
-        if (VMODE == 3 && (k < V.klo || k >= V.khi)) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) *V.pg(k, lid, r) = emg::zero<T>();
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) *V.p(k, lid, r) = emg::zero<T>();
-        }
+        for (int r = 0; r < 4; ++r) *V.p(k, lid, r) = emg::zero<T>();
         *V.p4(k, lid) = emg::zero<T>();
     }
     __syncthreads();
@@ -1093,14 +948,13 @@ __global__ __launch_bounds__(LC_THREADS, BATCH ? 2 : 1) void k_line_colour(emg::
     const int half = wave & 1;
     const int qline = line0 + (wave >> 1) * 16 + ((threadIdx.x & 63) >> 2), j = threadIdx.x & 3;
     const int qend = line0 + nl;
-    constexpr bool SPLIT = VMODE == 3;
-    if (half == 0) quad_forward<T, 0, QD, SPLIT, FT>(A.n0(), n0p, nlines, qline, qend, j, fac, lfac, V, dum, dum4);
-    else quad_forward<T, 1, QD, SPLIT, FT>(A.n0(), n0p, nlines, qline, qend, j, fac, lfac, V, dum, dum4);
+    if (half == 0) quad_forward<T, 0, QD, FT>(A.n0(), n0p, nlines, qline, qend, j, fac, lfac, V, dum, dum4);
+    else quad_forward<T, 1, QD, FT>(A.n0(), n0p, nlines, qline, qend, j, fac, lfac, V, dum, dum4);
     __syncthreads();
     // the backward pass stores into the FIELD; its dummy slots must be global memory too, or
     // the address select mixes address spaces and the stores become flat instructions
-    if (half == 0) quad_backward<T, DIR, 0, QD, BATCH, SPLIT, FT>(L, colour, cntp, cntq, n0p, qline, qend, j, fac, lfac, V, dummy, boff);
-    else quad_backward<T, DIR, 1, QD, BATCH, SPLIT, FT>(L, colour, cntp, cntq, n0p, qline, qend, j, fac, lfac, V, dummy, boff);
+    if (half == 0) quad_backward<T, DIR, 0, QD, BATCH, FT>(L, colour, cntp, cntq, n0p, qline, qend, j, fac, lfac, V, dummy, boff);
+    else quad_backward<T, DIR, 1, QD, BATCH, FT>(L, colour, cntp, cntq, n0p, qline, qend, j, fac, lfac, V, dummy, boff);
 }
 
 // ---- the colour pass of SMALL levels with short dependent chains: k_line_wide ----------------------------
@@ -1459,8 +1313,8 @@ __global__ __launch_bounds__(LW_THREADS + 64) void k_line_wide(emg::Level<T> L, 
 // workgroup barrier (LDS-only: the chains' factor prefetch stays in flight) per R steps. The producers
 // also put the raw right-hand sides of the rows the middle block reads (row m, and entry 0 of row
 // m + 1) into the records.
-//   RD : depth of the factor prefetch ring in the chain waves (4 for one source; 2 for B >= 2: a step
-//        of B sources takes B times as long, so two steps ahead is as far ahead in time).
+// Everything else about an instantiation follows from (DIR, B, COMPACT): stream_producers, stream_depth and
+// stream_lf_ring below, and the paired stores of quad_backward_stream.
 // lfo != nullptr: also the eight coupling entries of the item's block (stencil.h: line_coupling -- from the zeta
 // values the right-hand side needs anyway) into the coupling ring [2 halves][R rows][lpw lines][8]
 template <class T, int DIR>
@@ -1500,13 +1354,31 @@ __device__ __forceinline__ void stream_produce(const emg::Axes<T, DIR> &A, int c
     }
 }
 
-constexpr int LS_PROD = 384;                 // producer threads of k_line_stream for groups (6 waves; one source: 4; + 2 chain waves)
+// Producer threads of k_line_stream (+ 2 chain waves): four waves for one source with fp64 records (in a config-3 cycle
+// six measure the same to 0.5 %: tools/ab_cycle.py); six for groups and for compact records -- those kernels are held
+// to 256 registers by their chain waves' SIMD partners anyway, so two more cost nothing and keep more loads in flight.
+constexpr int stream_producers(int B, bool compact) { return (B >= 2 || compact) ? 384 : 256; }
+// Depth of the factor prefetch ring in the chain waves, in block steps. Groups: 2 (a step of B sources takes B times
+// as long, so two steps ahead is as far ahead in time). One source: LINE_PAD, and 8 with compact records on x-lines (a
+// compact ring entry holds 12 instead of 24 registers) -- same-box A/B at 256^3, ms per launch x / y / z: fp64 records
+// 0.885 / 0.955 / 0.969, compact with 4: 0.817 / 0.757 / 0.748, with 8: 0.740 / 0.794 / 0.789 (the producers of y / z
+// lines, whose gathers use half of every cache line, are what the chains wait for: more chain loads in flight delay
+// them; x-line producers read whole lines).
+// (Measured and not kept -- profiles/r06_compact_line_kernel_ab.txt: two workgroups of four waves per CU with 8 rows per
+// chunk, 0.915 / 0.761 / 0.773 ms per launch against 0.817 / 0.757 / 0.748; four producer waves instead of six, 0.732 /
+// 0.780 / 0.770 against 0.697 / 0.766 / 0.764; the w records of the rows nearest the middle block in LDS, +4-10 %.)
+constexpr int stream_depth(int dir, int B, bool compact) { return B >= 2 ? 2 : (compact && dir == 0) ? 8 : emg::LINE_PAD; }
+// One source (B == 1) takes the coupling entries of a block (the 8 reals of its lfac record) from a second LDS ring
+// [2 buffers][2 halves][R][lpw][8] behind the first: the producers, which hold the zeta values already, recompute them
+// -- 64 B per block less to fetch in the forward pass, 32 B less in the backward pass. Groups fetch the lfac records
+// (for groups of two the second ring leaves room for 8 rows per chunk only: y / z lines 0.83 -> 0.79-0.82 x per source,
+// x-lines 0.82 -> 0.93 x -- measured, not adopted).
+constexpr bool stream_lf_ring(int B) { return B == 1; }
 
 // forward half-chain that takes its right-hand sides from the LDS ring, for B right-hand sides
-// LFR: the coupling entries come from the coupling ring (lfring), not from the lfac records
 // FT / WT: storage types of the T records / the w records (T, or emg::compact_of<T>); vec: the w records of the
 // group's first source as WT, source b's b * vstride elements (of WT) behind them
-template <class T, int HALF, int RD, int B, bool LFR, class FT = T, class WT = T>
+template <class T, int HALF, int RD, int B, class FT = T, class WT = T>
 __device__ __forceinline__ void quad_forward_stream(int n0, int n0p, int nlines, int qline, int qend, int line0, int j,
                                                       const FT *fac, const double *lfac, WT *vec, size_t vstride,
                                                       size_t dummy_off, const T *ringbase, int lpw, int R, int nchunks,
@@ -1519,8 +1391,9 @@ __device__ __forceinline__ void quad_forward_stream(int n0, int n0p, int nlines,
     const VecRef<WT> V = VecRef<WT>::global(vec, nlines);
     WT *const dummy = vec + dummy_off;                           // (every source's scratch has its dummy slots)
     WT *const dslot = dummy + ((threadIdx.x & 63) >> 2) * 5;
+    constexpr bool LFR = stream_lf_ring(B);
     QuadRow<T, FT> ring[RD];
-    using LAddr = LaneAddr<T, HALF, false, FT, WT>;
+    using LAddr = LaneAddr<T, HALF, FT, WT>;
     const LAddr LA(fac, lfac, nlines, line, j, V);
     auto fetch = [&](QuadRow<T, FT> &q, int i) { q.template load<LAddr, false, !LFR>(LA, W.fwd(W.clampi(i))); };
 #pragma unroll
@@ -1602,7 +1475,7 @@ __device__ __forceinline__ void stream_produce_w(const WT *vec, int nlines, int 
 // the w records come from the LDS ring (stream_produce_w)
 // vec / vstride as in quad_forward_stream (WT); fdummy: dummy store targets of FIELD type for surplus quads and
 // padding blocks (global memory, like the field)
-template <class T, int DIR, int HALF, int RD, int B, bool PAIR, bool LFR, class FT = T, class WT = T>
+template <class T, int DIR, int HALF, int RD, int B, class FT = T, class WT = T>
 __device__ __forceinline__ void quad_backward_stream(const emg::Level<T> &L, int colour, int cntp, int cntq, int n0p, int qline,
                                                 int qend, int line0, int j, const FT *fac, const double *lfac, WT *vec,
                                                 size_t vstride, T *fdummy, size_t boff0, const T *ringbase, int lpw, int R,
@@ -1631,8 +1504,9 @@ __device__ __forceinline__ void quad_backward_stream(const emg::Level<T> &L, int
     const size_t fstep = active ? bs : 0;                     // per-source step of the field pointers
 
     const VecRef<WT> V = VecRef<WT>::global(vec, nlines);
+    constexpr bool LFR = stream_lf_ring(B);
     QuadRow<T, FT> ring[RD];
-    using LAddr = LaneAddr<T, HALF, false, FT, WT>;
+    using LAddr = LaneAddr<T, HALF, FT, WT>;
     const LAddr LA(fac, lfac, nlines, line, j, V);
     auto fetch = [&](QuadRow<T, FT> &q, int i) {
         q.template load<LAddr, false, !LFR>(LA, min(max(W.bwd(W.clampi(i)), HALF), n0p - 1));
@@ -1670,7 +1544,8 @@ __device__ __forceinline__ void quad_backward_stream(const emg::Level<T> &L, int
     const long incj = active ? (HALF ? sj : -sj) : 0, inc4 = active ? (HALF ? s4 : -s4) : 0;
     const double nz = j != 0 ? 1.0 : 0.0;
     const size_t srcelems = (size_t)2 * R * lpw * 5, bufelems = (size_t)B * srcelems;
-    constexpr bool PAIRED = PAIR && DIR == 0 && RD % 2 == 0;  // (steps come in pairs: W.steps is a multiple of 4)
+    // groups on x-lines store in pairs (one source: unpaired stores measure the same to 0.5 %)
+    constexpr bool PAIRED = B >= 2 && DIR == 0 && RD % 2 == 0;  // (steps come in pairs: W.steps is a multiple of 4)
     T hold_j[B], hold_4[B];
     T *hold_oj = dj, *hold_o4 = d4;
     size_t hold_step = 0;
@@ -1724,22 +1599,21 @@ __device__ __forceinline__ void quad_backward_stream(const emg::Level<T> &L, int
     }
 }
 
-// NPROD: producer threads (four waves for a single source; six for groups -- with the kernel held to 256
-// registers by its six waves anyway, two more producer waves cost nothing and keep more loads in flight)
-// LFR: the coupling entries (the 8 reals of a block's lfac record) are recomputed by the producers and handed
-// over through a second ring [2 buffers][2 halves][R][lpw][8] behind the first: 64 B per block less to fetch in
-// the forward pass (the producers hold the zeta values already), 32 B less in the backward pass.
+// B: right-hand sides of the group (producer waves, ring depth, coupling ring: stream_producers / stream_depth /
+// stream_lf_ring above).
 // COMPACT: the T records (`facv`) and the w records (in the scratch) are stored as emg::compact_of<T> -- single
 // precision, rounded once when the set-up / the forward pass stores them and widened when they are loaded; the
 // right-hand sides, the rings, every operation and the solution stay in T. 120 + 2 x 40 instead of 240 + 2 x 80
 // of the ~1 210 B a block costs per colour pass on the levels that live in HBM.
-template <class T, int DIR, int B, int RD, int NPROD, bool PAIR, bool LFR, bool COMPACT = false>
-__global__ __launch_bounds__(128 + NPROD, 1) void k_line_stream(emg::Level<T> L, int colour, int cntp, int cntq, int n0p,
+template <class T, int DIR, int B, bool COMPACT>
+__global__ __launch_bounds__(128 + stream_producers(B, COMPACT), 1) void k_line_stream(emg::Level<T> L, int colour, int cntp, int cntq, int n0p,
                                                                     int lpw, int R, const void *facv, const double *lfac,
                                                                     T *vecT, size_t vstrideT, size_t boff0)
 {
     // vecT: the scratch of the group's first right-hand side (source b's: b * vstrideT elements of T behind it);
     // boff0: element offset of the group's first source in the field / source buffers
+    constexpr int RD = stream_depth(DIR, B, COMPACT), NPROD = stream_producers(B, COMPACT);
+    constexpr bool LFR = stream_lf_ring(B);
     using FT = typename std::conditional<COMPACT, typename emg::compact_of<T>::type, T>::type;
     using WT = FT;
     const FT *const fac = reinterpret_cast<const FT *>(facv);
@@ -1817,11 +1691,11 @@ __global__ __launch_bounds__(128 + NPROD, 1) void k_line_stream(emg::Level<T> L,
     const int half = wave & 1;
     const int qline = line0 + ((threadIdx.x & 63) >> 2), j = threadIdx.x & 3;
     const int qend = line0 + nl;
-    if (half == 0) quad_forward_stream<T, 0, RD, B, LFR, FT, WT>(n0, n0p, nlines, qline, qend, line0, j, fac, lfac, vec, vstride, dummy_off, ringbase, lpw, R, nchunks, lfring);
-    else quad_forward_stream<T, 1, RD, B, LFR, FT, WT>(n0, n0p, nlines, qline, qend, line0, j, fac, lfac, vec, vstride, dummy_off, ringbase, lpw, R, nchunks, lfring);
+    if (half == 0) quad_forward_stream<T, 0, RD, B, FT, WT>(n0, n0p, nlines, qline, qend, line0, j, fac, lfac, vec, vstride, dummy_off, ringbase, lpw, R, nchunks, lfring);
+    else quad_forward_stream<T, 1, RD, B, FT, WT>(n0, n0p, nlines, qline, qend, line0, j, fac, lfac, vec, vstride, dummy_off, ringbase, lpw, R, nchunks, lfring);
     __syncthreads();
-    if (half == 0) quad_backward_stream<T, DIR, 0, RD, B, PAIR, LFR, FT, WT>(L, colour, cntp, cntq, n0p, qline, qend, line0, j, fac, lfac, vec, vstride, fdummy, boff0, ringbase, lpw, R, nchunks, lfring);
-    else quad_backward_stream<T, DIR, 1, RD, B, PAIR, LFR, FT, WT>(L, colour, cntp, cntq, n0p, qline, qend, line0, j, fac, lfac, vec, vstride, fdummy, boff0, ringbase, lpw, R, nchunks, lfring);
+    if (half == 0) quad_backward_stream<T, DIR, 0, RD, B, FT, WT>(L, colour, cntp, cntq, n0p, qline, qend, line0, j, fac, lfac, vec, vstride, fdummy, boff0, ringbase, lpw, R, nchunks, lfring);
+    else quad_backward_stream<T, DIR, 1, RD, B, FT, WT>(L, colour, cntp, cntq, n0p, qline, qend, line0, j, fac, lfac, vec, vstride, fdummy, boff0, ringbase, lpw, R, nchunks, lfring);
 }
 
 // End of the spelled-out section: back to the mode the translation unit is compiled with -- -ffp-contract=fast-honor-
@@ -1950,12 +1824,10 @@ __global__ void k_blocks_to_amat(T *amat, T *bvec, const T *middle, const double
 enum LineKind { LK_SEPARATE = 0, LK_COLOUR = 1, LK_STREAM = 3 };
 struct LinePlan {
     int kind;        // LineKind
-    int vmode;       // LK_COLOUR: where the records live (k_line_colour's VMODE 0..3)
+    int vmode;       // LK_COLOUR: where the records live (k_line_colour's VMODE 0..2)
     int lpw;         // lines per workgroup
-    int R;           // LK_STREAM / LK_STREAM: rows per chunk of the right-hand-side ring
     size_t smem;     // dynamic LDS of the launch
     bool shortl;     // the records were laid out with the short granule (lines of <= LINE_SHORT blocks)
-    bool batchk;     // LK_COLOUR: the instantiation with the batch as a grid dimension
 };
 // largest group of right-hand sides one k_line_stream workgroup serves (its chain quads hold a factor
 // row once and apply it to all of them)
@@ -1970,22 +1842,17 @@ inline int stream_rows(int g, size_t elem, bool lfr = false)
 }
 template <class T> LinePlan line_plan(const emg::LineClass &lc, int batch)
 {
-    LinePlan P{LK_SEPARATE, 0, 16, 0, 0, emg::line_pad(lc.n0) == emg::LINE_PAD_SHORT, false};
-    if (!(g_line_fuse == 1 || (g_line_fuse == 2 && lc.lines <= g_line_fuse_max))) return P;
+    LinePlan P{LK_SEPARATE, 0, 16, 0, emg::line_pad(lc.n0) == emg::LINE_PAD_SHORT};
+    if (!g_line_fuse) return P;
     P.kind = LK_COLOUR;
     // lines per workgroup: as few as keeps the workgroup count within one per CU
     int lpw = 16;
     if (g_line_lpw > 0) lpw = g_line_lpw;
     else if (cdiv(lc.lines, 4) * batch <= 256) lpw = 4;      // all right-hand sides count
     else if (cdiv(lc.lines, 8) * batch <= 256) lpw = 8;
-    // records in LDS if they fit (+ the dummy slots) and every workgroup gets a CU;
-    // line_lds = 2: whenever they fit, with fewer lines per workgroup if the lines are too
-    // long for 16 (experiment)
+    // records in LDS if they fit (+ the dummy slots) and every workgroup gets a CU
     const size_t lds_cu = 160 * 1024;
     auto rec_bytes = [&](int l, int w) { return ((size_t)l * lc.n0p * w + emg::LINE_DUMMY) * sizeof(T); };
-    if (g_line_lds == 2 && g_line_lpw == 0) {
-        while (lpw > 4 && rec_bytes(lpw, 4) > lds_cu) lpw /= 2;
-    }
     P.lpw = lpw;
     const unsigned nwg = cdiv(lc.lines, lpw);
     // (the QD = 4 kernels hold more than 256 registers: one workgroup per CU whatever its LDS use,
@@ -1993,15 +1860,13 @@ template <class T> LinePlan line_plan(const emg::LineClass &lc, int batch)
     // their records in LDS only while every workgroup of the launch gets a CU at once)
     const bool one_per_cu = !P.shortl && batch == 1;
     auto fits = [&](size_t smem) {
-        return g_line_lds && smem <= lds_cu &&
-               (g_line_lds >= 2 || one_per_cu || (size_t)nwg <= 256 * (lds_cu / smem));
+        return g_line_lds && smem <= lds_cu && (one_per_cu || (size_t)nwg <= 256 * (lds_cu / smem));
     };
     const size_t smem1 = rec_bytes(lpw, 5);
     const size_t smem2 = rec_bytes(lpw, 4);
-    P.batchk = batch > 1 || g_line_occ2;
     // (streaming also the levels whose whole records fit -- 64-block lines and shorter -- measured slower: 84.5
     // against 83.8 ms per config-3 cycle)
-    const bool streamable = g_line_stream && !P.shortl && !g_line_occ2 && !(g_line_debug & 1) && lpw <= 16 && !fits(smem1) &&
+    const bool streamable = g_line_stream && !P.shortl && lpw <= 16 && !fits(smem1) &&
                             (!fits(smem2) || g_line_stream >= 2);
     // the largest levels of a single-source solve: right-hand sides streamed through LDS
     // (where slots 0..3 of the records fit in LDS -- 128-block lines -- k_line_colour's mode 2 is as fast:
@@ -2016,7 +1881,7 @@ template <class T> LinePlan line_plan(const emg::LineClass &lc, int batch)
     // factors fetched once per group (k_line_stream)
     // (also where slots 0..3 of the records of ONE source would fit in LDS: with the batch as a grid dimension
     // those launches fetch the factors once per source)
-    const bool streamable_b = g_line_stream && !P.shortl && !g_line_occ2 && !(g_line_debug & 1) && lpw == 16 && !fits(smem1);
+    const bool streamable_b = g_line_stream && !P.shortl && lpw == 16 && !fits(smem1);
     if (streamable_b && batch > 1 && g_line_stream_bmin > 0 && lc.n0 >= g_line_stream_bmin) {
         P.kind = LK_STREAM;
         return P;
@@ -2025,12 +1890,6 @@ template <class T> LinePlan line_plan(const emg::LineClass &lc, int batch)
         if (fits(smem1)) { P.vmode = 1; P.smem = smem1; }
     } else if (fits(smem1)) { P.vmode = 1; P.smem = smem1; }
     else if (fits(smem2)) { P.vmode = 2; P.smem = smem2; }
-    else if (g_line_lds >= 3 && batch == 1 && !g_line_occ2 && lpw == 16) {
-        // line_lds = 3 (experiment): lines too long for mode 2 keep the record rows around the
-        // middle block in LDS, the outer rows in the global scratch (mode 3)
-        const emg::LineSplit sp = emg::line_split_rows(lc.n0, lc.n0p, lpw, sizeof(T));
-        if (sp.lds_bytes > 0) { P.vmode = 3; P.smem = sp.lds_bytes; P.batchk = false; }
-    }
     return P;
 }
 
@@ -2040,10 +1899,14 @@ inline bool line_wide_used(int dir, int nx, int ny, int nz)
     return g_line_wide > 0 && emg::line_n0(dir, nx, ny, nz) <= g_line_wide && emg::line_nfac_elems(dir, nx, ny, nz) > 0;
 }
 
-// Does direction `dir` of this level keep COMPACT line factors (k_line_stream<.., COMPACT>)? The level asks for it
-// (emg3d_level::flags, or option line_compact = 1), and every colour class of the direction runs the streamed kernel
-// for the level's number of right-hand sides (one source, or groups of them) -- the set-up (which stores the T records
-// in that form), the size query and the launcher all decide with this one function of the level and the options.
+// Does direction `dir` of this level keep COMPACT line factors? The level asks for it (emg3d_level::flags, or option
+// line_compact = 1), and every colour class of the direction runs, for any number of right-hand sides, ONE of the two
+// kinds of kernel that read them: k_line_stream<.., COMPACT>, or the fused k_line_colour on lines of more than
+// LINE_SHORT blocks (record modes 0..2, all of which have an instantiation over compact T records). The set-up (which
+// stores the T records in that form), the size query and the launcher all decide with this one function of the level
+// and the options. The plans it refuses -- separate launches (line_fuse = 0), the short granule, k_line_wide -- are
+// the only ones without a compact instantiation, and a plan is a function of the class, the batch and the options
+// alone: the launcher, which runs what the plan says, cannot meet compact records it has no kernel for (it checks).
 template <class T> bool line_compact_used(const emg::Level<T> &L, int dir)
 {
     if (g_line_compact < 0 || !(g_line_compact > 0 || (L.flags & emg::LEVEL_LINE_COMPACT))) return false;
@@ -2063,7 +1926,7 @@ template <class T> bool line_compact_used(const emg::Level<T> &L, int dir)
         // batch -- such a level keeps fp64 records for everybody (PI: the plan of a very large batch).
         const LinePlan P1 = line_plan<T>(lc, 1), PB = line_plan<T>(lc, L.batch), PI = line_plan<T>(lc, 1 << 10);
         auto ok = [](const LinePlan &P) {
-            return P.kind == LK_STREAM || (P.kind == LK_COLOUR && !P.shortl && P.vmode >= 0 && P.vmode <= 2 && g_line_compact_colour);
+            return P.kind == LK_STREAM || (P.kind == LK_COLOUR && !P.shortl);
         };
         if (!ok(P1) || !ok(PB) || !ok(PI) || P1.kind != PB.kind || P1.kind != PI.kind) return false;
         any = true;
@@ -2073,47 +1936,42 @@ template <class T> bool line_compact_used(const emg::Level<T> &L, int dir)
 
 template <class T, int DIR, int B>
 void launch_stream_group(const emg::Level<T> &L, int c, const emg::LineClass &lc, const void *f, const double *lf, T *vec,
-                         size_t vstride, int b0, int lpw, hipStream_t st, bool compact = false)
+                         size_t vstride, int b0, int lpw, hipStream_t st, bool compact)
 {
-    // one source: the coupling entries through a second ring (option line_stream_lf, default 1)
-    // (for groups of two the second ring leaves room for 8 rows per chunk only: y / z lines 0.83 -> 0.79-0.82 x per
-    // source, x-lines 0.82 -> 0.93 x -- measured, not adopted)
-    const bool lfr = B == 1 && (g_line_stream_lf != 0 || compact);
+    constexpr bool lfr = stream_lf_ring(B);
     int R = stream_rows(B, sizeof(T), lfr);
+    // rows per ring chunk of the compact single-source kernel: 16 for x-lines (their producers read 16 consecutive blocks of
+    // a line as one contiguous segment), 8 for y / z lines (same-box A/B at 256^3: x 0.709 -> 0.775, y 0.785 -> 0.764,
+    // z 0.780 -> 0.766 ms per launch with 8) unless option line_stream_r names a value
+    if (B == 1 && compact && DIR != 0 && g_line_stream_r == 0 && R > 8) R = 8;
     const size_t smem = (size_t)2 * B * 2 * R * lpw * 5 * sizeof(T) + (lfr ? (size_t)2 * 2 * R * lpw * 8 * sizeof(double) : 0);
-    // one source: four producer waves and unpaired stores (in a config-3 cycle six waves / paired x-line stores
-    // measure the same to 0.5 %: tools/ab_cycle.py); groups: six producer waves, x-line stores in pairs
-    constexpr int RD = B >= 2 ? 2 : emg::LINE_PAD;
-    constexpr int NPROD = B >= 2 ? LS_PROD : 256;
-    const void *kern = lfr ? (const void *)&k_line_stream<T, DIR, B, RD, NPROD, (B >= 2), (B == 1)>
-                           : (const void *)&k_line_stream<T, DIR, B, RD, NPROD, (B >= 2), false>;
-    int nprod = NPROD;
-    size_t smem_c = smem;
-    if constexpr (B >= 2) {
-        if (compact) kern = (const void *)&k_line_stream<T, DIR, B, RD, NPROD, true, false, true>;
-    }
-    if constexpr (B == 1) {
-        const bool rd8 = g_line_compact_rd == 8 || (g_line_compact_rd == 0 && DIR == 0);
-        if (compact) {
-            kern = rd8 ? (const void *)&k_line_stream<T, DIR, 1, 8, LS_PROD_COMPACT, false, true, true>
-                       : (const void *)&k_line_stream<T, DIR, 1, RD, LS_PROD_COMPACT, false, true, true>;
-            nprod = LS_PROD_COMPACT;
-        }
-        // rows per ring chunk of the compact kernel: 16 for x-lines (their producers read 16 consecutive blocks of a line as
-        // one contiguous segment), 8 for y / z lines (same-box A/B at 256^3: x 0.709 -> 0.775, y 0.785 -> 0.764, z 0.780 ->
-        // 0.766 ms per launch with 8) unless option line_stream_r names a value
-        if (compact && DIR != 0 && g_line_stream_r == 0 && R > 8) {
-            R = 8;
-            smem_c = (size_t)2 * 2 * R * lpw * 5 * sizeof(T) + (size_t)2 * 2 * R * lpw * 8 * sizeof(double);
-        }
-    }
+    const void *kern = compact ? (const void *)&k_line_stream<T, DIR, B, true> : (const void *)&k_line_stream<T, DIR, B, false>;
     (void)allow_lds(kern, 160 * 1024);
     T *v0 = vec + (size_t)b0 * vstride;
     size_t boff0 = (size_t)b0 * L.bstride;
     const unsigned nwg = cdiv(lc.lines, lpw);
     void *args[] = {(void *)&L, (void *)&c, (void *)&lc.cntp, (void *)&lc.cntq, (void *)&lc.n0p, (void *)&lpw, (void *)&R,
                     (void *)&f, (void *)&lf, (void *)&v0, (void *)&vstride, (void *)&boff0};
-    (void)hipLaunchKernel(kern, dim3(nwg), dim3(128 + nprod), args, smem_c, st);
+    (void)hipLaunchKernel(kern, dim3(nwg), dim3(128 + stream_producers(B, compact)), args, smem, st);
+}
+
+// One k_line_colour launch: VM = where the records live (the kernel's VMODE), QDV = padding granule of the records,
+// FT = storage type of the T records (T, or emg::compact_of<T>::type: line_compact_used)
+template <class T, int DIR, int VM, int QDV, class FT>
+void launch_lc(const emg::Level<T> &L, int c, const emg::LineClass &lc, const LinePlan &P, const FT *f, const double *lf,
+               T *vec, size_t vstride, hipStream_t st)
+{
+    const unsigned nwg = cdiv(lc.lines, P.lpw);
+    T *const dummy = vec + (vstride - emg::LINE_DUMMY);
+    if (L.batch > 1) {
+        if (VM != 0) (void)allow_lds((const void *)&k_line_colour<T, DIR, VM, true, QDV, FT>, 160 * 1024);
+        hipLaunchKernelGGL((k_line_colour<T, DIR, VM, true, QDV, FT>), dim3(nwg, L.batch), dim3(LC_THREADS), P.smem, st, L, c,
+                           lc.cntp, lc.cntq, lc.n0p, P.lpw, f, lf, vec, dummy, vstride);
+    } else {
+        if (VM != 0) (void)allow_lds((const void *)&k_line_colour<T, DIR, VM, false, QDV, FT>, 160 * 1024);
+        hipLaunchKernelGGL((k_line_colour<T, DIR, VM, false, QDV, FT>), dim3(nwg), dim3(LC_THREADS), P.smem, st, L, c,
+                           lc.cntp, lc.cntq, lc.n0p, P.lpw, f, lf, vec, dummy, vstride);
+    }
 }
 
 template <class T, int DIR>
@@ -2165,65 +2023,25 @@ int launch_line_colour(const emg::Level<T> &L, int c, const T *fac, const double
         }
         return 0;
     }
+    // line_compact_used admits only plans that read compact records (see there): anything else here is a bug in it
+    if (compact && (P.kind != LK_COLOUR || P.shortl))
+        return fail(EMG3D_ERR_INTERNAL, "gauss_seidel: compact line factors on a level whose plan cannot read them");
     if (P.kind == LK_COLOUR) {
-        const int lpw = P.lpw;
-        const unsigned nwg = cdiv(lc.lines, lpw);
-        const size_t lds_cu = 160 * 1024;
         constexpr int P4 = emg::LINE_PAD, P2 = emg::LINE_PAD_SHORT;
-        (void)allow_lds(reinterpret_cast<const void *>(&k_line_colour<T, DIR, 1, false, P4>), lds_cu);
-        (void)allow_lds(reinterpret_cast<const void *>(&k_line_colour<T, DIR, 2, false, P4>), lds_cu);
-        (void)allow_lds(reinterpret_cast<const void *>(&k_line_colour<T, DIR, 1, true, P4>), lds_cu);
-        (void)allow_lds(reinterpret_cast<const void *>(&k_line_colour<T, DIR, 2, true, P4>), lds_cu);
-        (void)allow_lds(reinterpret_cast<const void *>(&k_line_colour<T, DIR, 3, false, P4>), lds_cu);
-#define LC_LAUNCH(VM, QDV)                                                                                               \
-    do {                                                                                                                 \
-        if (L.batch > 1 || (g_line_occ2 && VM == 0))                                                                     \
-            hipLaunchKernelGGL((k_line_colour<T, DIR, VM, true, QDV>), dim3(nwg, L.batch), dim3(LC_THREADS), P.smem, st, L, \
-                               c, lc.cntp, lc.cntq, lc.n0p, lpw, f, lf, vec, vec + dummy_off, vstride);                  \
-        else                                                                                                             \
-            hipLaunchKernelGGL((k_line_colour<T, DIR, VM, false, QDV>), dim3(nwg), dim3(LC_THREADS), P.smem, st, L, c,    \
-                               lc.cntp, lc.cntq, lc.n0p, lpw, f, lf, vec, vec + dummy_off,                               \
-                               (VM == 0 && (g_line_debug & 1)) ? ~(size_t)0 : vstride);                                  \
-    } while (0)
-        // compact T records (line_compact_used): the same kernel reading single-precision factor rows
-#define LC_LAUNCH_C(VM)                                                                                                  \
-    do {                                                                                                                 \
-        const FT *fc = reinterpret_cast<const FT *>(fv);                                                                 \
-        (void)allow_lds(reinterpret_cast<const void *>(&k_line_colour<T, DIR, VM, false, P4, FT>), lds_cu);              \
-        (void)allow_lds(reinterpret_cast<const void *>(&k_line_colour<T, DIR, VM, true, P4, FT>), lds_cu);               \
-        if (L.batch > 1)                                                                                                 \
-            hipLaunchKernelGGL((k_line_colour<T, DIR, VM, true, P4, FT>), dim3(nwg, L.batch), dim3(LC_THREADS), P.smem, st, \
-                               L, c, lc.cntp, lc.cntq, lc.n0p, lpw, fc, lf, vec, vec + dummy_off, vstride);              \
-        else                                                                                                             \
-            hipLaunchKernelGGL((k_line_colour<T, DIR, VM, false, P4, FT>), dim3(nwg), dim3(LC_THREADS), P.smem, st, L, c, \
-                               lc.cntp, lc.cntq, lc.n0p, lpw, fc, lf, vec, vec + dummy_off, vstride);                    \
-    } while (0)
         if (compact) {
-            if (P.shortl || P.vmode > 2 || g_line_occ2 || (g_line_debug & 1)) {
-                return fail(EMG3D_ERR_BADARG, "gauss_seidel: compact line factors under options that cannot read them");
-            }
-            if (P.vmode == 1) LC_LAUNCH_C(1);
-            else if (P.vmode == 2) LC_LAUNCH_C(2);
-            else LC_LAUNCH_C(0);
-            return 0;
-        }
-        if (P.shortl) {
-            if (P.vmode == 1) LC_LAUNCH(1, P2);
-            else LC_LAUNCH(0, P2);
-        } else if (P.vmode == 1) LC_LAUNCH(1, P4);
-        else if (P.vmode == 2) LC_LAUNCH(2, P4);
-        else if (P.vmode == 3)
-            hipLaunchKernelGGL((k_line_colour<T, DIR, 3, false, P4>), dim3(nwg), dim3(LC_THREADS), P.smem, st, L, c,
-                               lc.cntp, lc.cntq, lc.n0p, lpw, f, lf, vec, vec + dummy_off, vstride);
-        else LC_LAUNCH(0, P4);
-#undef LC_LAUNCH
-#undef LC_LAUNCH_C
+            const FT *fc = reinterpret_cast<const FT *>(fv);
+            if (P.vmode == 1) launch_lc<T, DIR, 1, P4>(L, c, lc, P, fc, lf, vec, vstride, st);
+            else if (P.vmode == 2) launch_lc<T, DIR, 2, P4>(L, c, lc, P, fc, lf, vec, vstride, st);
+            else launch_lc<T, DIR, 0, P4>(L, c, lc, P, fc, lf, vec, vstride, st);
+        } else if (P.shortl) {
+            if (P.vmode == 1) launch_lc<T, DIR, 1, P2>(L, c, lc, P, f, lf, vec, vstride, st);
+            else launch_lc<T, DIR, 0, P2>(L, c, lc, P, f, lf, vec, vstride, st);
+        } else if (P.vmode == 1) launch_lc<T, DIR, 1, P4>(L, c, lc, P, f, lf, vec, vstride, st);
+        else if (P.vmode == 2) launch_lc<T, DIR, 2, P4>(L, c, lc, P, f, lf, vec, vstride, st);
+        else launch_lc<T, DIR, 0, P4>(L, c, lc, P, f, lf, vec, vstride, st);
         return 0;
     }
     // separate launches (option line_fuse = 0): the right-hand sides one after the other
-    if (compact) {
-        return fail(EMG3D_ERR_BADARG, "gauss_seidel: compact line factors need the fused line kernels (line_fuse)");
-    }
     for (int b = 0; b < L.batch; ++b) {
         const emg::Level<T> Lb = emg::source_level(L, b);
         T *const vb = vec + (size_t)b * vstride;
@@ -2274,22 +2092,13 @@ int launch_gs(const emg3d_level *lv, int lr, int nu, const void *fac, const doub
             // eta sums: tile-major buffer (stored halves when the level's eta are purely imaginary
             // or the field is real), or formed on the fly when fac == NULL
             const int st = !fac ? 0 : pst_mode<T>(L.flags);
-            int pf = (g_point_prefetch >= 0 && g_point_prefetch <= 3) ? g_point_prefetch : 0;
-            if (st == 0 && pf == 2) pf = 1;      // 24 eta loads per node in flight twice do not fit the registers
-#define PT_ROW(B, PF_)                                                                                         \
-    {(const void *)&k_gs_point_tile<T, TB, 0, B, PF_>, (const void *)&k_gs_point_tile<T, TB, 2, B, PF_>,          \
-     (const void *)&k_gs_point_tile<T, TB, 3, B, PF_>}
-            const void *kfn[2][4][3] = {{PT_ROW(false, 0), PT_ROW(false, 1), PT_ROW(false, 2), PT_ROW(false, 3)},
-                                        {PT_ROW(true, 0), PT_ROW(true, 1), PT_ROW(true, 2), PT_ROW(true, 3)}};
-#undef PT_ROW
-            const void *kern = kfn[L.batch > 1 ? 1 : 0][pf][st == 0 ? 0 : st - 1];
-            // single-precision eta sums: the instantiations without software prefetch (the default) only
-            if (st == emg::PST_HALF_F32)
-                kern = L.batch > 1 ? (const void *)&k_gs_point_tile<T, TB, emg::PST_HALF_F32, true, 0>
-                                   : (const void *)&k_gs_point_tile<T, TB, emg::PST_HALF_F32, false, 0>;
-            if (st == emg::PST_FULL_F32)
-                kern = L.batch > 1 ? (const void *)&k_gs_point_tile<T, TB, emg::PST_FULL_F32, true, 0>
-                                   : (const void *)&k_gs_point_tile<T, TB, emg::PST_FULL_F32, false, 0>;
+            const bool bt = L.batch > 1;
+#define PT_KERN(ST) (bt ? (const void *)&k_gs_point_tile<T, TB, ST, true> : (const void *)&k_gs_point_tile<T, TB, ST, false>)
+            const void *const kern = st == 0 ? PT_KERN(0)
+                                     : st == emg::PST_FULL ? PT_KERN(emg::PST_FULL)
+                                     : st == emg::PST_HALF ? PT_KERN(emg::PST_HALF)
+                                     : st == emg::PST_HALF_F32 ? PT_KERN(emg::PST_HALF_F32) : PT_KERN(emg::PST_FULL_F32);
+#undef PT_KERN
             HIP_TRY(allow_lds(kern, smem));
             // A sweep ends with the pair of tile colours the next sweep (opposite direction) starts
             // with, and nothing else runs in between: those tiles do the node colours of BOTH sweeps
@@ -2549,19 +2358,30 @@ extern "C" {
 int emg3d_version(void) { return EMG3D_AMD_VERSION; }
 const char *emg3d_last_error(void) { return g_err.c_str(); }
 
-// run-time options: name -> variable (documented where the variables are declared)
-struct OptionEntry { const char *name; int *value; };
+// run-time options: name -> variable and admissible range (documented in include/emg3d_amd.h and where the
+// variables are declared)
+struct OptionEntry { const char *name; int *value; int lo = INT_MIN, hi = INT_MAX; };
 static const OptionEntry g_options[] = {
-    {"point_slab", &g_point_slab},       {"point_tile_min", &g_point_tile_min}, {"line_fuse", &g_line_fuse},
-    {"line_fuse_max", &g_line_fuse_max}, {"skip_repeat", &g_skip_repeat},       {"tile_fuse", &g_tile_fuse},
-    {"line_lds", &g_line_lds},           {"point_prefetch", &g_point_prefetch}, {"residual_zb", &g_residual_zb},
-    {"line_occ2", &g_line_occ2},         {"point_small", &g_point_small},       {"line_lpw", &g_line_lpw},
-    {"line_debug", &g_line_debug},       {"line_stream", &g_line_stream},       {"line_stream_r", &g_line_stream_r},
-    {"line_order", &g_line_order},       {"point_order", &emg::point_order_ref()},
-    {"line_stream_bmin", &g_line_stream_bmin}, {"line_stream_lf", &g_line_stream_lf}, {"residual_roll", &g_residual_roll},
-    {"line_wide", &g_line_wide},         {"line_wide_bt", &g_line_wide_bt},     {"line_compact", &g_line_compact},
-    {"line_compact_rd", &g_line_compact_rd}, {"point_compact", &g_point_compact},
-    {"line_compact_colour", &g_line_compact_colour},
+    {"point_slab", &g_point_slab},
+    {"point_tile_min", &g_point_tile_min},
+    {"line_fuse", &g_line_fuse},
+    {"skip_repeat", &g_skip_repeat},
+    {"tile_fuse", &g_tile_fuse},
+    {"line_lds", &g_line_lds, 0, 1},
+    {"residual_zb", &g_residual_zb},
+    {"point_small", &g_point_small},
+    {"line_lpw", &g_line_lpw},                       // (a set: emg3d_set_option)
+    {"line_stream", &g_line_stream},
+    {"line_stream_r", &g_line_stream_r, 0, 32},
+    {"line_order", &g_line_order, 0, 2},
+    {"point_order", &emg::point_order_ref(), 0, 1},
+    {"line_stream_bmin", &g_line_stream_bmin},
+    {"residual_roll", &g_residual_roll},
+    // (lines longer than WIDE_N0_MAX hold no N records: a larger value would be a silent no-op)
+    {"line_wide", &g_line_wide, 0, emg::WIDE_N0_MAX},
+    {"line_wide_bt", &g_line_wide_bt},               // (a set: emg3d_set_option)
+    {"line_compact", &g_line_compact, -1, 1},
+    {"point_compact", &g_point_compact, -1, 1},
 };
 constexpr int N_OPTIONS = sizeof(g_options) / sizeof(g_options[0]);
 static int g_options_generation = 0;      // bumped whenever an option changes its value
@@ -2572,30 +2392,23 @@ const char *emg3d_option_name(int i) { return (i >= 0 && i < N_OPTIONS) ? g_opti
 int emg3d_set_option(const char *name, int value)
 {
     if (!name) return fail(EMG3D_ERR_BADARG, "set_option: null name");
-    if (!std::strcmp(name, "residual_zb") && value < 1) value = 1;
-    if (!std::strcmp(name, "line_lpw") && value != 0 && value != 4 && value != 8 && value != 16 && value != 32)
-        return fail(EMG3D_ERR_BADARG, "line_lpw: 0, 4, 8, 16 or 32");
-    // line_debug produces WRONG fields by design (timing experiments): only with the environment's consent
-    if (!std::strcmp(name, "line_debug") && value != 0 && !std::getenv("EMG3D_AMD_ALLOW_DEBUG"))
-        return fail(EMG3D_ERR_BADARG, "line_debug: wrong results by design; set EMG3D_AMD_ALLOW_DEBUG=1 to use it");
-    // rows per chunk of k_line_stream's ring: whole register rings of LINE_PAD blocks (a chunk that ends inside a
-    // ring pass would be read past its end), and two chunks x two halves x 16 lines must fit the LDS of a CU
-    if (!std::strcmp(name, "line_stream_r") && value != 0 && (value < 4 || value > 32 || value % emg::LINE_PAD != 0))
-        return fail(EMG3D_ERR_BADARG, "line_stream_r: 0 (= 16) or a multiple of 4 in 4..32");
-    // (lines longer than WIDE_N0_MAX hold no N records: a larger value would be a silent no-op)
-    if (!std::strcmp(name, "line_wide") && (value < 0 || value > emg::WIDE_N0_MAX)) return fail(EMG3D_ERR_BADARG, "line_wide: 0 .. 64");
-    if (!std::strcmp(name, "line_wide_bt") && value != 0 && value != 192 && value != 256) return fail(EMG3D_ERR_BADARG, "line_wide_bt: 0, 192 or 256");
-    if (!std::strcmp(name, "line_compact_rd") && value != 0 && value != 4 && value != 8) return fail(EMG3D_ERR_BADARG, "line_compact_rd: 0, 4 or 8");
-    if (!std::strcmp(name, "point_compact") && (value < -1 || value > 1)) return fail(EMG3D_ERR_BADARG, "point_compact: -1, 0 or 1");
-    if (!std::strcmp(name, "line_compact") && (value < -1 || value > 1)) return fail(EMG3D_ERR_BADARG, "line_compact: -1, 0 or 1");
-    if (!std::strcmp(name, "line_order") && (value < 0 || value > 2)) return fail(EMG3D_ERR_BADARG, "line_order: 0, 1 or 2");
-    if (!std::strcmp(name, "point_order") && (value < 0 || value > 1)) return fail(EMG3D_ERR_BADARG, "point_order: 0 or 1");
-    for (const OptionEntry &o : g_options)
-        if (!std::strcmp(name, o.name)) {
-            if (*o.value != value) ++g_options_generation;
-            *o.value = value;
-            return 0;
+    for (const OptionEntry &o : g_options) {
+        if (std::strcmp(name, o.name)) continue;
+        if (o.value == &g_residual_zb && value < 1) value = 1;
+        bool ok = value >= o.lo && value <= o.hi;
+        if (o.value == &g_line_lpw) ok = value == 0 || value == 4 || value == 8 || value == 16 || value == 32;
+        // rows per chunk of k_line_stream's ring: whole register rings of LINE_PAD blocks (a chunk that ends inside a
+        // ring pass would be read past its end), and two chunks x two halves x 16 lines must fit the LDS of a CU
+        if (o.value == &g_line_stream_r) ok = ok && value % emg::LINE_PAD == 0;
+        if (o.value == &g_line_wide_bt) ok = value == 0 || value == 192 || value == 256;
+        if (!ok) {
+            g_err = std::string("set_option: ") + name + " = " + std::to_string(value) + " is not an admissible value";
+            return EMG3D_ERR_BADARG;
         }
+        if (*o.value != value) ++g_options_generation;
+        *o.value = value;
+        return 0;
+    }
     return fail(EMG3D_ERR_BADARG, "set_option: unknown option");
 }
 

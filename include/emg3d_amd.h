@@ -70,6 +70,7 @@ extern "C" {
 #define EMG3D_ERR_BADARG (-1)
 #define EMG3D_ERR_NODEVICE (-2)
 #define EMG3D_ERR_SCRATCH (-3)
+#define EMG3D_ERR_INTERNAL (-4) /* the library contradicted itself (a bug, not a caller's error) */
 
 /* One grid level with device-resident arrays (emg3d_dev_* flavour). */
 typedef struct emg3d_level {
@@ -120,51 +121,62 @@ int emg3d_version(void);
 const char *emg3d_last_error(void);
 /* number of visible HIP devices (0 without a GPU; never fails) */
 int emg3d_device_count(void);
-/* Tuning knobs; all but "point_tile_min", "line_order", "point_order" (the order of the sweeps) and "line_wide" (the
- * rounding of the short-line solves) never change results. "point_slab": plane-slab thickness of the point
- * smoother's launch schedule (0 = one launch per colour over all planes). "point_tile_min"
- * DOES select the sweep order of the point smoother (see above; <= 0 never tiled). "line_lds":
- * 1 (default) keeps the right-hand-side / solution records of a fused line launch in LDS
- * when they fit, 0 always uses the global scratch. "line_lpw": lines per workgroup of a fused
- * line launch (4, 8, 16, 32; 0 = automatic; with 32 the streamed kernels, whose two chain waves serve
- * 16 lines, are not used). "line_fuse":
- * 0 three launches per colour and line direction (rhs, forward, backward), 1 one fused
- * launch, 2 (default) fused for colour classes with at most "line_fuse_max" lines (default:
- * no limit -- the fused launch is the faster one at every size measured). "skip_repeat": 1
- * (default) does not launch the colour pass that repeats the last colour class of the previous
- * sweep of the same call (it reproduces the same values bit by bit); 0 launches every pass.
- * "tile_fuse": 1 (default) lets the tiles of the tiled point smoother where two consecutive
- * sweeps meet run both sweeps on one LDS copy (same operations, one load / store less).
- * "line_stream": 2 (default) runs the colour passes of lines whose records do not fit the LDS of a CU (~128
- * blocks and more with 16 lines per workgroup) with the right-hand sides and coupling entries (forward pass)
- * and the w records (backward pass) staged through LDS rings by producer waves while the chain waves substitute
- * (k_line_stream: no round trip of the right-hand sides through the scratch, bit-identical results); 1 only
- * where not even slots 0..3 of the records fit (~160 blocks and more); 0 the
- * three-phase kernel everywhere. "line_stream_lf": 1 (default) one source's coupling entries are recomputed by the
- * producers instead of fetched (bit-equal values). "line_stream_r": rows per
- * half of that ring (0 = 16; a multiple of 4 in 4..32, anything else is refused; fewer where several
- * right-hand sides share the LDS). "line_stream_bmin": with several right-hand sides
- * (emg3d_level::batch > 1) such passes on lines of at least this many blocks (default 64; <= 0: never)
- * serve GROUPS of up to four right-hand sides per workgroup, every factor row fetched once per group
- * (k_line_stream<.., B>; per source the same arithmetic: bit-identical to separate solves) -- with the batch
- * as a grid dimension every source's workgroups fetch the factors again.
- * "line_wide": lines of at most this many blocks (default 33; 0 = never; only on levels small enough to hold one more
- * 16-entry record per block) are solved by k_line_wide: the same direct solve of the line system as the other line
- * kernels (emg3d/core.py:1481-1616) with the same factors, but with the block recurrences restated in four unknowns
- * through the model-only matrices N_k = (T_k C_k)[1..4, 1..4], which are one more rounding of T_k C_k -- fields agree
- * with the other kernels' to rounding (~1e-13 per call), not bit for bit. A level runs the same kernel for every
- * right-hand side, alone or in a batch, so batched and separate solves stay bit-identical under any value.
- * "line_order" and "point_order" DO select the order of the sweeps (see above), like
- * "point_tile_min".
- * "line_compact": 0 (default) compact line records where the level asks for them (EMG3D_LEVEL_LINE_COMPACT), 1 on
- * every level whose direction streams (tests, timing), -1 never (the flag is ignored). CHANGES the rounding of the
- * streamed line solves (see EMG3D_LEVEL_LINE_COMPACT).
- * "point_compact": the same three values for the eta sums of the tiled point smoother (EMG3D_LEVEL_POINT_COMPACT).
- * "line_compact_rd" (0 = 8 for x-lines, 4 else; 4 | 8): prefetch depth of the chain waves of the compact streamed
- * kernel; no influence on results.
- * "line_debug" is for timing experiments only (bit 0 aliases the records of a line: WRONG
- * results); a non-zero value is refused unless the environment variable EMG3D_AMD_ALLOW_DEBUG is set.
- * Out-of-range values of "line_order" (0..2) and "point_order" (0..1) are refused (EMG3D_ERR_BADARG). */
+/* Run-time options. A name that is not in the list below is refused: emg3d_set_option returns EMG3D_ERR_BADARG,
+ * emg3d_get_option returns -1. So is a value outside the stated set (the value then stays as it was), except where a
+ * clamp is noted. Options marked (R) change results -- the order of the sweeps or a rounding; all others never do.
+ *
+ * Point smoother
+ *   "point_tile_min" (R)  levels with at least this many interior nodes use the tiled schedule, which sweeps in
+ *                         another order (see above). Default 1 << 20; <= 0 never, 1 always.
+ *   "point_order" (R)     0 | 1: sequence of the node colours (see above).
+ *   "point_compact" (R)   -1 | 0 | 1: single-precision eta sums of the tiled smoother: 0 (default) where the level asks
+ *                         for them (EMG3D_LEVEL_POINT_COMPACT), 1 on every tiled level (tests, timing), -1 never.
+ *   "point_slab"          plane-slab thickness of the plain launch schedule (0, default: one launch per colour over
+ *                         all planes).
+ *   "point_small"         levels with at most this many interior nodes (default 512; 0: off) run all passes of a call in
+ *                         one single-workgroup launch.
+ *   "tile_fuse"           1 (default): the tiles where two consecutive sweeps of a call meet run both sweeps on one LDS
+ *                         copy (same operations, one load / store less); 0: every sweep on its own.
+ *   "skip_repeat"         1 (default): the colour pass that repeats the last colour class of the previous sweep of the
+ *                         same call is not launched (it reproduces the same values bit by bit); 0: every pass. Point
+ *                         and line smoothers.
+ * Line smoothers
+ *   "line_order" (R)      0 | 1 | 2: sequence of the colour passes (see above).
+ *   "line_wide" (R)       0 .. 64: lines of at most this many blocks (default 33; 0: never; only on levels small enough
+ *                         to hold one more 16-entry record per block) are solved by k_line_wide: the same direct solve of
+ *                         the line system (emg3d/core.py:1481-1616) with the same factors, the block recurrences
+ *                         restated in four unknowns through N_k = (T_k C_k)[1..4, 1..4], one more rounding of T_k C_k --
+ *                         fields agree with the other kernels' to rounding (~1e-13 per call), not bit for bit. A level
+ *                         runs the same kernel for every right-hand side, so batched and separate solves stay bit-
+ *                         identical under any value.
+ *   "line_wide_bt"        0 | 192 | 256: block threads of a k_line_wide workgroup (0, default: whichever gives a
+ *                         workgroup more lines).
+ *   "line_compact" (R)    -1 | 0 | 1: single-precision line records: 0 (default) where the level asks for them
+ *                         (EMG3D_LEVEL_LINE_COMPACT), 1 on every level whose kernels can read them (tests, timing),
+ *                         -1 never.
+ *   "line_fuse"           0: three launches per colour pass (right-hand sides, forward, backward); non-zero (default 2):
+ *                         one fused launch -- the faster one at every size measured.
+ *   "line_lds"            0 | 1: 1 (default) keeps the right-hand-side / solution records of a fused launch in LDS when
+ *                         they fit, 0 always uses the global scratch.
+ *   "line_lpw"            0 | 4 | 8 | 16 | 32: lines per workgroup of a fused launch (0, default: automatic; with 32 the
+ *                         streamed kernel, whose two chain waves serve 16 lines, is not used).
+ *   "line_stream"         2 (default): colour passes of lines whose records do not fit the LDS of a CU (~128 blocks and
+ *                         more with 16 lines per workgroup) run k_line_stream -- right-hand sides, coupling entries and
+ *                         w records staged through LDS rings by producer waves while the chain waves substitute
+ *                         (bit-identical to the three-phase kernel); 1: only where not even slots 0..3 of the records
+ *                         fit (~160 blocks and more); 0: the three-phase kernel everywhere.
+ *   "line_stream_r"       rows per half of that ring: 0 (default: 16, and 8 for compact y / z lines) or a multiple of 4
+ *                         in 4..32 (fewer where several right-hand sides share the LDS).
+ *   "line_stream_bmin"    with several right-hand sides (emg3d_level::batch > 1) such passes on lines of at least this
+ *                         many blocks (default 64; <= 0: never) serve GROUPS of up to four right-hand sides per
+ *                         workgroup, every factor row fetched once per group (per source the same arithmetic: bit-
+ *                         identical to separate solves) -- with the batch as a grid dimension every source's
+ *                         workgroups fetch the factors again.
+ * Residual
+ *   "residual_zb"         planes a workgroup walks on large levels (default 8; values below 1 are clamped to 1).
+ *   "residual_roll"       1 (default): operands a cell shares with the cell below it are carried in registers; 0: every
+ *                         cell loads all of its own.
+ * (Switches of earlier measurements that are gone: DESIGN.md, "Retired switches".) */
 int emg3d_set_option(const char *name, int value);
 int emg3d_get_option(const char *name);
 /* enumeration of the options (for callers that key cached state -- captured graphs, option-

@@ -435,17 +435,20 @@ def test_option_table_and_fingerprint():
     assert lib.emg3d_set_option(b'line_lpw', 5) != 0                      # only 0, 4, 8, 16, 32
     assert lib.emg3d_set_option(b'residual_zb', 0) == 0 and lib.emg3d_get_option(b'residual_zb') == 1
     lib.emg3d_set_option(b'residual_zb', 8)
-    # options that select the sweep order take their defined values only; the wrong-results debug switch
-    # needs the environment's consent
+    # options that select the sweep order take their defined values only
     assert lib.emg3d_set_option(b'line_order', 3) != 0 and lib.emg3d_set_option(b'point_order', 2) != 0
     assert lib.emg3d_get_option(b'line_order') == 1 and lib.emg3d_get_option(b'point_order') == 1
-    had = os.environ.pop('EMG3D_AMD_ALLOW_DEBUG', None)
-    try:
-        assert lib.emg3d_set_option(b'line_debug', 1) != 0 and lib.emg3d_get_option(b'line_debug') == 0
-        assert lib.emg3d_set_option(b'line_debug', 0) == 0
-    finally:
-        if had is not None:
-            os.environ['EMG3D_AMD_ALLOW_DEBUG'] = had
+    # the record modes of the fused line kernel: LDS when it fits (1) or never (0), nothing else
+    lds = lib.emg3d_get_option(b'line_lds')
+    assert lds in (0, 1)
+    for bad in (2, 3):
+        assert lib.emg3d_set_option(b'line_lds', bad) != 0 and lib.emg3d_get_option(b'line_lds') == lds
+    # the switches of past experiments are gone ("Retired switches"): unknown like any other name
+    for gone in (b'line_debug', b'line_occ2', b'point_prefetch', b'line_stream_lf', b'line_fuse_max',
+                 b'line_compact_colour', b'line_compact_rd'):
+        assert lib.emg3d_set_option(gone, 0) != 0 and lib.emg3d_set_option(gone, 1) != 0
+        assert lib.emg3d_get_option(gone) == -1
+        assert gone.decode() not in names
 
 
 def test_bench_helpers_without_a_gpu():

@@ -1,5 +1,6 @@
 """Per-kernel register / LDS / scratch usage of the HIP library as the compiler reports it
-(`hipcc -Rpass-analysis=kernel-resource-usage`; cross-compiles without a GPU).
+(`hipcc -Rpass-analysis=kernel-resource-usage`; cross-compiles without a GPU), compiled with the flags of the
+shipped build (emg3d_amd/_lib.py: HIPCC_FLAGS).
 
     python tools/kernel_resources.py [filter-substring]
 """
@@ -7,18 +8,25 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from emg3d_amd._lib import HIPCC_FLAGS  # noqa: E402
 
 
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ''
     src = os.path.join(ROOT, 'emg3d_amd', 'csrc', 'kernels.hip')
-    r = subprocess.run(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c', src, '-o', '/tmp/_kr.o',
-                        '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True)
+    flags = [f for f in HIPCC_FLAGS if f != '-shared']
+    with tempfile.TemporaryDirectory() as tmp:
+        r = subprocess.run([os.environ.get('HIPCC', 'hipcc')] + flags + ['-c', src, '-o', os.path.join(tmp, 'kernels.o'),
+                            '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise SystemExit(r.stderr[-4000:])
     cur, rows = None, []
     for line in r.stderr.splitlines():
-        m = re.search(r'remark: +(.*?) \[-Rpass', line)
+        m = re.search(r'remark: (?:\S+:\d+:\d+: +)?(.*?) \[-Rpass', line)     # (with or without file:line:col)
         if not m:
             continue
         t = m.group(1)
