@@ -21,6 +21,56 @@ __device__ __forceinline__ double grad_edge(cplx b, cplx e, cplx smu0)
 }
 __device__ __forceinline__ double grad_edge(double b, double e, double smu0) { return b * smu0 * e; }
 
+// The gather of one cell, shared with k_edges_to_cells (reciprocal.h): `edge.x(i)`, `.y(i)`, `.z(i)` give the real
+// edge value real(b s mu0 e) of x-, y-, z-edge i.
+template <class E>
+__device__ __forceinline__ void edges_to_cell(int nx, int ny, int ix, int iy, int iz, const E &edge, const double *vol,
+                                              double *gx, double *gy, double *gz)
+{
+    const size_t c = (size_t)ix + (size_t)nx * (iy + (size_t)ny * iz);
+    const double v = vol[c];
+#define IX(i, j, k) ((size_t)(i) + (size_t)nx * ((j) + (size_t)(ny + 1) * (k)))
+#define IY(i, j, k) ((size_t)(i) + (size_t)(nx + 1) * ((j) + (size_t)ny * (k)))
+#define IZ(i, j, k) ((size_t)(i) + (size_t)(nx + 1) * ((j) + (size_t)(ny + 1) * (k)))
+#define TERM(C, I) (v * edge.C(I) / 4)
+    {   // x-edges (ix; iy | iy+1; iz | iz+1): order of the reference's loop = z outer, y inner
+        double a = gx[c];
+        a += TERM(x, IX(ix, iy, iz));
+        a += TERM(x, IX(ix, iy + 1, iz));
+        a += TERM(x, IX(ix, iy, iz + 1));
+        a += TERM(x, IX(ix, iy + 1, iz + 1));
+        gx[c] = a;
+    }
+    {   // y-edges (ix | ix+1; iy; iz | iz+1): x inner
+        double a = gy[c];
+        a += TERM(y, IY(ix, iy, iz));
+        a += TERM(y, IY(ix + 1, iy, iz));
+        a += TERM(y, IY(ix, iy, iz + 1));
+        a += TERM(y, IY(ix + 1, iy, iz + 1));
+        gy[c] = a;
+    }
+    {   // z-edges (ix | ix+1; iy | iy+1; iz)
+        double a = gz[c];
+        a += TERM(z, IZ(ix, iy, iz));
+        a += TERM(z, IZ(ix + 1, iy, iz));
+        a += TERM(z, IZ(ix, iy + 1, iz));
+        a += TERM(z, IZ(ix + 1, iy + 1, iz));
+        gz[c] = a;
+    }
+#undef IX
+#undef IY
+#undef IZ
+#undef TERM
+}
+
+template <class T> struct GradEdges {       // real(b s mu0 e) from the two fields
+    const T *ex, *ey, *ez, *bx, *by, *bz;
+    T smu0;
+    __device__ __forceinline__ double x(size_t i) const { return grad_edge(bx[i], ex[i], smu0); }
+    __device__ __forceinline__ double y(size_t i) const { return grad_edge(by[i], ey[i], smu0); }
+    __device__ __forceinline__ double z(size_t i) const { return grad_edge(bz[i], ez[i], smu0); }
+};
+
 template <class T>
 __global__ __launch_bounds__(256) void k_gradient_accumulate(int nx, int ny, int nz, const T *ex, const T *ey, const T *ez,
                                                              const T *bx, const T *by, const T *bz, T smu0,
@@ -28,40 +78,7 @@ __global__ __launch_bounds__(256) void k_gradient_accumulate(int nx, int ny, int
 {
     const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y, iz = blockIdx.z;
     if (ix >= nx || iy >= ny) return;
-    const size_t c = (size_t)ix + (size_t)nx * (iy + (size_t)ny * iz);
-    const double v = vol[c];
-#define IX(i, j, k) ((size_t)(i) + (size_t)nx * ((j) + (size_t)(ny + 1) * (k)))
-#define IY(i, j, k) ((size_t)(i) + (size_t)(nx + 1) * ((j) + (size_t)ny * (k)))
-#define IZ(i, j, k) ((size_t)(i) + (size_t)(nx + 1) * ((j) + (size_t)(ny + 1) * (k)))
-#define TERM(B, E, I) (v * grad_edge(B[I], E[I], smu0) / 4)
-    {   // x-edges (ix; iy | iy+1; iz | iz+1): order of the reference's loop = z outer, y inner
-        double a = gx[c];
-        a += TERM(bx, ex, IX(ix, iy, iz));
-        a += TERM(bx, ex, IX(ix, iy + 1, iz));
-        a += TERM(bx, ex, IX(ix, iy, iz + 1));
-        a += TERM(bx, ex, IX(ix, iy + 1, iz + 1));
-        gx[c] = a;
-    }
-    {   // y-edges (ix | ix+1; iy; iz | iz+1): x inner
-        double a = gy[c];
-        a += TERM(by, ey, IY(ix, iy, iz));
-        a += TERM(by, ey, IY(ix + 1, iy, iz));
-        a += TERM(by, ey, IY(ix, iy, iz + 1));
-        a += TERM(by, ey, IY(ix + 1, iy, iz + 1));
-        gy[c] = a;
-    }
-    {   // z-edges (ix | ix+1; iy | iy+1; iz)
-        double a = gz[c];
-        a += TERM(bz, ez, IZ(ix, iy, iz));
-        a += TERM(bz, ez, IZ(ix + 1, iy, iz));
-        a += TERM(bz, ez, IZ(ix, iy + 1, iz));
-        a += TERM(bz, ez, IZ(ix + 1, iy + 1, iz));
-        gz[c] = a;
-    }
-#undef IX
-#undef IY
-#undef IZ
-#undef TERM
+    edges_to_cell(nx, ny, ix, iy, iz, GradEdges<T>{ex, ey, ez, bx, by, bz, smu0}, vol, gx, gy, gz);
 }
 
 }  // namespace
@@ -102,13 +119,12 @@ namespace {
 __device__ __forceinline__ cplx sens_edge(cplx nsmu0, cplx e, double q) { return (nsmu0 * e) * q; }
 __device__ __forceinline__ double sens_edge(double nsmu0, double e, double q) { return (nsmu0 * e) * q; }
 
-template <class T>
-__global__ __launch_bounds__(256) void k_sensitivity_source(int nx, int ny, int nz, const T *ex, const T *ey, const T *ez,
-                                                            T nsmu0, const double *vol, const double *vx, const double *vy,
-                                                            const double *vz, T *gx, T *gy, T *gz)
+// The gather of one node, shared with k_edge_weights (reciprocal.h): `edge.x(i, q)`, `.y(i, q)`, `.z(i, q)` take
+// q = 1/4 sum of volume * v over the cells of x-, y-, z-edge i.
+template <class E>
+__device__ __forceinline__ void cells_to_edges(int nx, int ny, int nz, int ix, int iy, int iz, const double *vol,
+                                               const double *vx, const double *vy, const double *vz, const E &edge)
 {
-    const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y, iz = blockIdx.z;
-    if (ix > nx || iy > ny || iz > nz) return;
     // cell (i, j, k) exists? -- the lower neighbours of the node are (ix-1, iy-1, iz-1)
     const bool x0 = ix > 0, x1 = ix < nx, y0 = iy > 0, y1 = iy < ny, z0 = iz > 0, z1 = iz < nz;
 #define CELL(i, j, k) ((size_t)(i) + (size_t)nx * ((j) + (size_t)ny * (k)))
@@ -119,8 +135,7 @@ __global__ __launch_bounds__(256) void k_sensitivity_source(int nx, int ny, int 
         ADD(vx, y1 && z0, ix, iy, iz - 1)
         ADD(vx, y0 && z1, ix, iy - 1, iz)
         ADD(vx, y1 && z1, ix, iy, iz)
-        const size_t i = (size_t)ix + (size_t)nx * (iy + (size_t)(ny + 1) * iz);
-        gx[i] = sens_edge(nsmu0, ex[i], a / 4);
+        edge.x((size_t)ix + (size_t)nx * (iy + (size_t)(ny + 1) * iz), a / 4);
     }
     if (y1) {   // y-edge: cells (ix-1 | ix, iy, iz-1 | iz)
         double a = 0.0;
@@ -128,8 +143,7 @@ __global__ __launch_bounds__(256) void k_sensitivity_source(int nx, int ny, int 
         ADD(vy, x1 && z0, ix, iy, iz - 1)
         ADD(vy, x0 && z1, ix - 1, iy, iz)
         ADD(vy, x1 && z1, ix, iy, iz)
-        const size_t i = (size_t)ix + (size_t)(nx + 1) * (iy + (size_t)ny * iz);
-        gy[i] = sens_edge(nsmu0, ey[i], a / 4);
+        edge.y((size_t)ix + (size_t)(nx + 1) * (iy + (size_t)ny * iz), a / 4);
     }
     if (z1) {   // z-edge: cells (ix-1 | ix, iy-1 | iy, iz)
         double a = 0.0;
@@ -137,11 +151,29 @@ __global__ __launch_bounds__(256) void k_sensitivity_source(int nx, int ny, int 
         ADD(vz, x1 && y0, ix, iy - 1, iz)
         ADD(vz, x0 && y1, ix - 1, iy, iz)
         ADD(vz, x1 && y1, ix, iy, iz)
-        const size_t i = (size_t)ix + (size_t)(nx + 1) * (iy + (size_t)(ny + 1) * iz);
-        gz[i] = sens_edge(nsmu0, ez[i], a / 4);
+        edge.z((size_t)ix + (size_t)(nx + 1) * (iy + (size_t)(ny + 1) * iz), a / 4);
     }
 #undef CELL
 #undef ADD
+}
+
+template <class T> struct SourceEdges {     // g = (-s mu0 e) q
+    const T *ex, *ey, *ez;
+    T nsmu0;
+    T *gx, *gy, *gz;
+    __device__ __forceinline__ void x(size_t i, double q) const { gx[i] = sens_edge(nsmu0, ex[i], q); }
+    __device__ __forceinline__ void y(size_t i, double q) const { gy[i] = sens_edge(nsmu0, ey[i], q); }
+    __device__ __forceinline__ void z(size_t i, double q) const { gz[i] = sens_edge(nsmu0, ez[i], q); }
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void k_sensitivity_source(int nx, int ny, int nz, const T *ex, const T *ey, const T *ez,
+                                                            T nsmu0, const double *vol, const double *vx, const double *vy,
+                                                            const double *vz, T *gx, T *gy, T *gz)
+{
+    const int ix = blockIdx.x * blockDim.x + threadIdx.x, iy = blockIdx.y * blockDim.y + threadIdx.y, iz = blockIdx.z;
+    if (ix > nx || iy > ny || iz > nz) return;
+    cells_to_edges(nx, ny, nz, ix, iy, iz, vol, vx, vy, vz, SourceEdges<T>{ex, ey, ez, nsmu0, gx, gy, gz});
 }
 
 }  // namespace

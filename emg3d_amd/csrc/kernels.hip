@@ -2832,3 +2832,4 @@ int emg3d_core_solve(void *amat, void *bvec, int n, int is_complex)
 #include "receivers.h"
 #include "krylov.h"
 #include "adjoint.h"
+#include "reciprocal.h"

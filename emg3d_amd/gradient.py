@@ -44,6 +44,10 @@ Convention: ``jtvec`` returns the real array with ``sum(v * jtvec(y)) == Re sum_
 every real ``v`` -- which makes ``misfit_and_gradient == jtvec(residual * weights)`` the gradient of
 ``sum w |r|^2 / 2``.
 
+``ReciprocalSensitivity`` keeps one more field per (receiver, frequency), the solution for a unit datum at that
+receiver; A being complex symmetric, both products are then reductions over the kept fields and solve nothing
+(DESIGN.md 4.12).
+
 Limits as in the reference: no epsilon_r / mu_r.
 """
 import numpy as np
@@ -51,7 +55,8 @@ import numpy as np
 from emg3d_amd import fields, models
 from emg3d_amd.fields import Field
 
-__all__ = ['misfit_and_gradient', 'residual_source_field', 'Sensitivity', 'jvec', 'jtvec', 'expand_vector']
+__all__ = ['misfit_and_gradient', 'residual_source_field', 'Sensitivity', 'ReciprocalSensitivity', 'jvec', 'jtvec',
+           'expand_vector']
 
 _DCHAIN = {          # d sigma / d property, applied to the gradient w.r.t. conductivity (emg3d/maps.py:120-330)
     'Conductivity': lambda g, p: g,
@@ -135,20 +140,29 @@ _NCOMP = {'isotropic': 1, 'HTI': 2, 'VTI': 2, 'triaxial': 3}
 _EXPAND = {'isotropic': (0, 0, 0), 'HTI': (0, 1, 0), 'VTI': (0, 0, 1), 'triaxial': (0, 1, 2)}
 
 
-def _vector_components(model, vector):
-    """The model-shaped ``vector`` of ``jvec`` as (n, nx, ny, nz) floats after the derivative chain of the
-    mapping, ``vector_k * d sigma / d property_k`` -- n = 1 (isotropic), 2 (HTI: x, y; VTI: x, z) or 3."""
+_PROPS = {'isotropic': ('property_x',), 'HTI': ('property_x', 'property_y'), 'VTI': ('property_x', 'property_z'),
+          'triaxial': ('property_x', 'property_y', 'property_z')}
+
+
+def _check_vector(model, vector):
+    """The model-shaped ``vector`` of ``jvec`` as (n, nx, ny, nz) floats -- n = 1 (isotropic), 2 (HTI: x, y; VTI:
+    x, z) or 3; raises unless it is real and shaped like the model's properties."""
     n, shape = _NCOMP[model.case], tuple(model.grid.shape_cells)
     v = np.asarray(vector)
     allowed = [(n,) + shape] + ([shape] if n == 1 else [])
     if v.shape not in allowed or np.iscomplexobj(v):
         raise ValueError(f"`vector` must be real with shape {' or '.join(str(a) for a in allowed[::-1])} "
                          f"for a model of case '{model.case}'. Provided: {v.dtype} {v.shape}.")
-    v = np.array(v, dtype=np.float64).reshape((n,) + shape)
-    props = {'isotropic': ('property_x',), 'HTI': ('property_x', 'property_y'), 'VTI': ('property_x', 'property_z'),
-             'triaxial': ('property_x', 'property_y', 'property_z')}[model.case]
+    return np.asarray(v, dtype=np.float64).reshape((n,) + shape)
+
+
+def _vector_components(model, vector):
+    """The model-shaped ``vector`` of ``jvec`` as (n, nx, ny, nz) floats after the derivative chain of the
+    mapping, ``vector_k * d sigma / d property_k`` -- n = 1 (isotropic), 2 (HTI: x, y; VTI: x, z) or 3."""
+    v = _check_vector(model, vector)
     chain = _DCHAIN[model.mapping]
-    return np.stack([chain(v[k], np.asarray(getattr(model, name), dtype=float)) for k, name in enumerate(props)])
+    return np.stack([chain(v[k], np.asarray(getattr(model, name), dtype=float))
+                     for k, name in enumerate(_PROPS[model.case])])
 
 
 def expand_vector(model, vector):
@@ -359,6 +373,14 @@ class Sensitivity:
         return [c for _, c in chunks]
 
     # ------------------------------------------------------------------------------- jvec ---
+    @staticmethod
+    def _cells_on_device(comps, dev):
+        """Cell arrays (nx, ny, nz) as flat device tensors, x fastest, as the kernels index them (the transposition
+        of a C-ordered array runs on the device)."""
+        import torch
+        return [torch.from_numpy(np.ascontiguousarray(c)).to(dev).permute(2, 1, 0).contiguous().reshape(-1)
+                for c in comps]
+
     def jvec(self, vector):
         """Sensitivity times a model-shaped real ``vector`` -- shape (nx, ny, nz) or (1, ...) isotropic,
         (2, ...) HTI / VTI, (3, ...) tri-axial, as ``Simulation.jvec``: dict (src, freq) -> complex array
@@ -370,9 +392,7 @@ class Sensitivity:
         comps = _vector_components(self.model, vector)          # raises on a wrong shape, before any GPU work
         dev = self._device()
         expand = _EXPAND[self.model.case]
-        # (cells x fastest, as the kernels index them; the transposition of a C-ordered array runs on the device)
-        on_model = [torch.from_numpy(np.ascontiguousarray(c)).to(dev).permute(2, 1, 0).contiguous().reshape(-1)
-                    for c in comps]
+        on_model = self._cells_on_device(comps, dev)
         regridded = {0: on_model}
         opts = {**self.opts, 'tol': self.tol_gradient}
         out = {}
@@ -415,16 +435,21 @@ class Sensitivity:
         return self._gather(out)
 
     # ------------------------------------------------------------------------------ jtvec ---
-    def jtvec(self, vector):
-        """Adjoint of the sensitivity times a data-shaped ``vector`` -- dict (src, freq) -> complex array
-        (n_receivers), NaN or a missing pair: no datum --: real array shaped like the gradient of
-        ``misfit_and_gradient``, with ``sum(v * jtvec(y)) == Re sum conj(y) * jvec(v)``. One solve per pair at
-        ``tol_gradient`` against the kept forward field; all-reduced over the ranks."""
+    def _check_data(self, vector):
+        """Raises unless every entry of the data-shaped ``vector`` has one value per receiver; their number."""
         nrec = len(self._rec[0])
         for pair, y in vector.items():
             if np.shape(y) != (nrec,):
                 raise ValueError(f"`vector[{pair!r}]` must have shape ({nrec},): one value per receiver. "
                                  f"Provided: {np.shape(y)}.")
+        return nrec
+
+    def jtvec(self, vector):
+        """Adjoint of the sensitivity times a data-shaped ``vector`` -- dict (src, freq) -> complex array
+        (n_receivers), NaN or a missing pair: no datum --: real array shaped like the gradient of
+        ``misfit_and_gradient``, with ``sum(v * jtvec(y)) == Re sum conj(y) * jvec(v)``. One solve per pair at
+        ``tol_gradient`` against the kept forward field; all-reduced over the ranks."""
+        nrec = self._check_data(vector)
 
         def data(pair, synthetic):
             y = vector.get(pair)
@@ -524,9 +549,335 @@ class Sensitivity:
             dist.all_reduce(m)
             grad, tm = g, m
         misfit = float(tm.cpu()[0])
+        return misfit, self._gradient_on_host(grad)
+
+    def _gradient_on_host(self, grad):
+        """The cell gradient with respect to the three conductivity components (device, 3 x n_cells, x fastest) as
+        the model-shaped array of the model's own properties (step 8 of the module docstring)."""
+        mgrid = self.model.grid
+        ncell = mgrid.n_cells
         g3 = np.stack([grad[k * ncell:(k + 1) * ncell].cpu().numpy().reshape(mgrid.shape_cells, order='F')
                        for k in range(3)])
-        return misfit, _finish_gradient(self.model, g3)
+        return _finish_gradient(self.model, g3)
+
+
+class ReciprocalSensitivity(Sensitivity):
+    """``Sensitivity`` whose ``jvec`` and ``jtvec`` solve nothing: next to the forward field of every (source,
+    frequency) it keeps one field per (receiver, frequency),
+
+        x_r = A^-1 residual_source_field(unit datum at receiver r alone)          (at ``tol_gradient``).
+
+    The system matrix is complex symmetric (``jtvec`` back-propagates with A, not its adjoint) and the receiver
+    operator does not depend on the source, so ``P_r A^-1 g = (A^-1 p_r)^T g`` and, per frequency,
+
+        jvec(v)[s, r] = conj(-s mu0) sum_k w_k e_s[k] x_r[k]         w = cells_to_edges(volumes * v), real
+        jtvec(y)      = cells(real(s mu0 t)),    t[k] = sum_s e_s[k] sum_r conj(y[s, r]) x_r[k]
+
+    -- reductions over the kept fields, bound by HBM (``emg3d_dev_edge_weights`` + ``emg3d_dev_sensitivity_dots``;
+    ``emg3d_dev_sensitivity_combine`` + ``emg3d_dev_edges_to_cells``): no solve, no hierarchy and no receiver
+    interpolation in a Gauss-Newton inner iteration. The price: ``n_receivers`` more solves per frequency in
+    ``forward()`` (batched by ``solve_batch`` under the rules of ``Sensitivity``'s ``batch``) and their fields.
+
+    Parameters as ``Sensitivity``, except: ``keep`` is ``'device'`` (two HBM stacks per frequency, [n_sources x
+    n_edges] and [n_receivers x n_edges]) or ``'host'`` (pinned stacks; a frequency's two stacks are uploaded into
+    one reused staging pair when that frequency is processed) -- ``False`` is refused; all pairs of a frequency must
+    share ONE computational grid (with a grid per source the receiver fields are not shared); one process only.
+    ``n_solves``: ``{'forward', 'receiver', 'jvec', 'jtvec'}``, the last two stay 0. The solver infos of the receiver
+    solves: ``info[('receiver', r, frequency name)]``; ``setup_seconds``: wall time ``forward()`` spent in the source
+    and in the receiver solves."""
+
+    def __init__(self, model, sources, frequencies, receivers, solver_opts=None, tol_gradient=1e-5, costs=None,
+                 grids=None, interpolate_opts=None, magnetic=None, keep='device', batch=1):
+        super().__init__(model, sources, frequencies, receivers, solver_opts=solver_opts, tol_gradient=tol_gradient,
+                         costs=costs, grids=grids, interpolate_opts=interpolate_opts, magnetic=magnetic, keep=keep,
+                         batch=batch)
+        if not self.keep:
+            raise ValueError("`keep` must be 'device' or 'host' for ReciprocalSensitivity: without kept fields there "
+                             f"is nothing to be solve-free from. Provided: {keep!r}.")
+        if self.world > 1:
+            raise NotImplementedError("ReciprocalSensitivity runs in one process; sharding frequencies over the ranks "
+                                      f"of a process group (here: {self.world}) is not implemented.")
+        mgrid = self.model.grid
+        shared = {}
+        for sname, fname in self.pairs:
+            g = self.grids.get((sname, fname)) if isinstance(self.grids, dict) else self.grids
+            g = mgrid if g is None or g == mgrid else g
+            first = shared.setdefault(fname, g)
+            if not (g is first or g == first):
+                raise ValueError(f"ReciprocalSensitivity: all pairs of frequency {fname!r} must share one computational "
+                                 f"grid (the receiver fields are shared by its sources); source {sname!r} has another.")
+        if isinstance(self.grids, dict):         # equal meshes of a frequency: ONE object, one set of per-grid tables
+            self.grids = {pair: shared[pair[1]] for pair in self.pairs}
+        self.n_solves = {'forward': 0, 'receiver': 0, 'jvec': 0, 'jtvec': 0}
+        self.setup_seconds = {'forward': 0.0, 'receiver': 0.0}
+
+    def _reset(self):
+        super()._reset()
+        self._stacks = {}            # frequency name -> [source fields (ns x n), receiver fields (nr x n)]
+        self._stage = None           # keep='host': the staging pair in HBM
+        self._dchain = None
+
+    def __repr__(self):
+        ns, nr, nf = len(self.sources), len(self._rec[0]), len(self.frequencies)
+        held = sum(len(t) for st in self._stacks.values() for t in st)
+        return (f"ReciprocalSensitivity: {len(self.pairs)} pairs ({ns} sources x {nf} frequencies), {nr * nf} receiver "
+                f"fields ({nr} receivers x {nf} frequencies); keep={self.keep!r}, batch={self.batch}; kept fields: {held} "
+                f"= {self.kept_bytes:,} B ({ {'device': 'HBM', 'host': 'pinned host memory'}[self.keep] })")
+
+    @property
+    def kept_bytes(self):
+        """Bytes held by the kept source and receiver fields ((n_sources + n_receivers) x n_edges x 16 B per
+        frequency, complex)."""
+        return int(sum(t.numel() * t.element_size() for st in self._stacks.values() for t in st))
+
+    # ----------------------------------------------------------------------------- set-up ---
+    def _new_stack(self, rows, n, dtype, dev):
+        import torch
+        if self.keep == 'host':
+            return torch.empty((rows, n), dtype=dtype, pin_memory=True)
+        need = rows * n * torch.empty(0, dtype=dtype).element_size()
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        if need > free:
+            raise MemoryError(f"ReciprocalSensitivity: a stack of {rows} kept fields needs {need:,} B of HBM, "
+                              f"{free:,} B are free; keep='host' holds the fields in pinned host memory instead.")
+        return torch.empty((rows, n), dtype=dtype, device=dev)
+
+    def _receiver_chunks(self):
+        """Receiver indices grouped for ``solve_batch`` under the rules of ``_chunks``."""
+        nrec = len(self._rec[0])
+        batched = (self.batch > 1 and not self._mag.any() and
+                   self.opts.get('sslsolver', True) in (True, False, None, 'bicgstab') and
+                   self.opts.get('cycle', 'F') is not None)
+        step = self.batch if batched else 1
+        return [list(range(r, min(r + step, nrec))) for r in range(0, nrec, step)]
+
+    def forward(self):
+        """The source solves at ``solver_opts['tol']`` (as ``Sensitivity``: same ``synthetic``), then the receiver
+        solves at ``tol_gradient``, frequency by frequency; once -- later calls return at once."""
+        if self._have_forward:
+            return self
+        import time
+        import torch
+        from emg3d_amd import solver
+        dev = self._device()
+        nrec = len(self._rec[0])
+
+        def lap(what=None, since=None):
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            if what:
+                self.setup_seconds[what] += now - since
+            return now
+        opts = {**self.opts, 'tol': self.tol_gradient}
+        for fname, freq in self.frequencies.items():
+            mine = [i for i in self._order if self.pairs[i][1] == fname]
+            if not mine:
+                continue
+            gkey, grid, gmodel, vol, plan = self._computational(self.pairs[mine[0]])
+            n = grid.n_edges
+            estack = xstack = None
+            clock = lap()
+            for row, i in enumerate(mine):
+                e, self._synthetic[i] = self._solve_forward(i)
+                if estack is None:
+                    estack = self._new_stack(len(mine), n, e.dtype, dev)
+                    xstack = self._new_stack(nrec, n, e.dtype, dev)
+                    self._stacks[fname] = [estack, xstack]
+                estack[row].copy_(e)
+                del e
+            clock = lap('forward', clock)
+            meta = Field(grid, frequency=freq)
+            for chunk in self._receiver_chunks():
+                rfields = []
+                for r in chunk:
+                    unit = np.full(nrec, np.nan, dtype=complex)
+                    unit[r] = 1.0
+                    rfields.append(residual_source_field(grid, freq, self.receivers, unit, np.ones(nrec), self._mag))
+                if len(chunk) == 1:
+                    hier = self._hierarchy(gkey, gmodel, meta)
+                    _, info = solver.solve(gmodel, rfields[0], return_info=True, always_return=True, hierarchy=hier,
+                                           _download=False, _sparse_source=True, **opts)
+                    back = [(hier.top.e, info)]
+                else:
+                    for rf in rfields:
+                        rf._trust_sparse = True
+                    hier = self._hierarchy(gkey, gmodel, meta, len(chunk))
+                    res = solver.solve_batch(gmodel, rfields, keep_fields=False, hierarchy=hier, _device_fields=True,
+                                             **opts)
+                    back = [(info.pop('_device_field', None), info) for _, info in res]
+                for r, (field, info) in zip(chunk, back):
+                    self.n_solves['receiver'] += 1
+                    self.info[('receiver', r, fname)] = info
+                    if field is None:                       # the solve failed: zero field, no contribution
+                        xstack[r].zero_()
+                    else:
+                        xstack[r].copy_(field[:n])
+                del back
+            lap('receiver', clock)
+        self._hier.clear()                   # the inner loop needs no hierarchy
+        self._have_forward = True
+        return self
+
+    def _fields_of(self, fname):
+        """The two stacks of a frequency in HBM (``keep='host'``: uploaded into the reused staging pair)."""
+        import torch
+        estack, xstack = self._stacks[fname]
+        if self.keep == 'device':
+            return estack, xstack
+        rows = [max(len(st[k]) for st in self._stacks.values()) for k in (0, 1)]
+        width = max(st[0].shape[1] for st in self._stacks.values())
+        if self._stage is None:
+            dev = self._device()
+            self._stage = [torch.empty(rows[k] * width, dtype=estack.dtype, device=dev) for k in (0, 1)]
+        out = []
+        for buf, host in zip(self._stage, (estack, xstack)):
+            view = buf[:host.numel()].view(host.shape)
+            view.copy_(host, non_blocking=False)
+            out.append(view)
+        return out
+
+    def _chain_factors(self, dev):
+        """d sigma / d property of the model's own properties (n x n_cells in HBM, cells x fastest): the derivative
+        chain of the mapping is a product with them, before G in ``jvec`` and after its transpose in ``jtvec``."""
+        import torch
+        if self._dchain is None:
+            chain, shape = _DCHAIN[self.model.mapping], tuple(self.model.grid.shape_cells)
+            self._dchain = torch.stack(self._cells_on_device(
+                [chain(np.ones(shape), np.asarray(getattr(self.model, name), dtype=float))
+                 for name in _PROPS[self.model.case]], dev))
+        return self._dchain
+
+    def _gradient_on_host(self, grad):
+        """``Sensitivity._gradient_on_host`` with the bookkeeping of ``_finish_gradient`` (same order) on the device:
+        only the model's own components cross to the host, laid out as the result."""
+        import torch
+        case, shape = self.model.case, tuple(self.model.grid.shape_cells)
+        g = grad.view(3, -1)
+        d = self._chain_factors(grad.device)
+        rows = [g[0]]
+        if case in ('HTI', 'triaxial'):
+            rows.append(g[1] * d[1])
+        else:
+            rows[0] = rows[0] + g[1]
+        if case in ('VTI', 'triaxial'):
+            rows.append(g[2] * d[-1])
+        else:
+            rows[0] = rows[0] + g[2]
+        rows[0] = rows[0] * d[0]
+        if len(rows) == 1:
+            return rows[0].cpu().numpy().reshape(shape, order='F')
+        # (n_cells, n) in memory = component fastest, then x: the Fortran order of the (n, nx, ny, nz) result
+        return torch.stack(rows, dim=1).cpu().numpy().reshape(-1).reshape((len(rows),) + shape, order='F')
+
+    def _per_frequency(self):
+        """(frequency name, pair indices, grid key, grid, cell volumes, averaging plan, s mu0) per frequency."""
+        for fname, freq in self.frequencies.items():
+            mine = [i for i in self._order if self.pairs[i][1] == fname]
+            if mine:
+                gkey, grid, gmodel, vol, plan = self._computational(self.pairs[mine[0]])
+                yield fname, mine, gkey, grid, vol, plan, complex(Field(grid, frequency=freq).smu0)
+
+    # ------------------------------------------------------------------------------- jvec ---
+    def jvec(self, vector):
+        """As ``Sensitivity.jvec``, without a solve: per frequency one ``emg3d_dev_edge_weights`` and one
+        ``emg3d_dev_sensitivity_dots`` over the kept fields."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        v = _check_vector(self.model, vector)                   # raises on a wrong shape, before any GPU work
+        dev = self._device()
+        self.forward()
+        expand = _EXPAND[self.model.case]
+        # the derivative chain of the mapping on the device: vector_k * d sigma / d property_k, cells x fastest
+        vdev = torch.from_numpy(np.ascontiguousarray(v)).to(dev).permute(0, 3, 2, 1).reshape(len(v), -1)
+        on_model = list(vdev * self._chain_factors(dev))
+        regridded = {0: on_model}
+        L = _lib.lib()
+        out = {}
+        for fname, mine, gkey, grid, vol, plan, smu0 in self._per_frequency():
+            if gkey not in regridded:            # linear volume average: the map whose adjoint is jtvec's way back
+                regridded[gkey] = [plan.on_device(c, log=False) for c in on_model]
+            vx, vy, vz = (regridded[gkey][k] for k in expand)
+            nx, ny, nz = grid.shape_cells
+            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
+            estack, xstack = self._fields_of(fname)
+            ns, nr = len(estack), len(xstack)
+            is_complex = int(estack.dtype == torch.complex128)
+            w = torch.empty(n, dtype=torch.float64, device=dev)
+            _lib.check(L.emg3d_dev_edge_weights(nx, ny, nz, _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(w),
+                                                _ptr(w, o1), _ptr(w, o2), _stream()), 'emg3d_dev_edge_weights')
+            # unit residual at a receiver: point source of strength conj(1 / (-s mu0)), times -s mu0 as every source
+            # (residual_source_field) = kappa p_r; jvec = p_r^T A^-1 (-s mu0 w e_s) = -s mu0 / kappa sum w e_s x_r
+            kappa = np.conj(1.0 / -smu0) * -smu0
+            scale = complex(-smu0 / kappa)
+            ws_len = L.emg3d_sensitivity_dots_ws_len(ns, nr, n)
+            ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+            res = torch.empty(ns * nr, dtype=estack.dtype, device=dev)
+            _lib.check(L.emg3d_dev_sensitivity_dots(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack),
+                                                    xstack.stride(0), nr, _ptr(w), scale.real, scale.imag, _ptr(res),
+                                                    _ptr(ws), ws_len, _stream()), 'emg3d_dev_sensitivity_dots')
+            res = res.cpu().numpy().reshape(ns, nr)
+            for row, i in enumerate(mine):
+                out[self.pairs[i]] = res[row].copy()
+        return {p: out[p] for p in self.pairs if p in out}
+
+    # ------------------------------------------------------------------------------ jtvec ---
+    def jtvec(self, vector):
+        """As ``Sensitivity.jtvec``, without a solve: per frequency one ``emg3d_dev_sensitivity_combine`` with the
+        coefficients ``conj(vector)`` (0 for NaN or a missing pair) and one ``emg3d_dev_edges_to_cells``."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        nrec = self._check_data(vector)
+        dev = self._device()
+        self.forward()
+        ncell = self.model.grid.n_cells
+        grad = torch.zeros(3 * ncell, dtype=torch.float64, device=dev)
+        L = _lib.lib()
+        for fname, mine, gkey, grid, vol, plan, smu0 in self._per_frequency():
+            coef = np.zeros((len(mine), nrec), dtype=complex)
+            for row, i in enumerate(mine):
+                y = vector.get(self.pairs[i])
+                if y is not None:
+                    coef[row] = np.conj(np.nan_to_num(np.asarray(y, dtype=complex), nan=0.0))
+            if not coef.any():
+                continue
+            nx, ny, nz = grid.shape_cells
+            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
+            estack, xstack = self._fields_of(fname)
+            is_complex = int(estack.dtype == torch.complex128)
+            cdev = torch.from_numpy(coef if is_complex else np.ascontiguousarray(coef.real)).to(dev)
+            t = torch.empty(n, dtype=estack.dtype, device=dev)
+            _lib.check(L.emg3d_dev_sensitivity_combine(n, is_complex, _ptr(estack), estack.stride(0), len(estack),
+                                                       _ptr(xstack), xstack.stride(0), len(xstack), _ptr(cdev), _ptr(t),
+                                                       _stream()), 'emg3d_dev_sensitivity_combine')
+            if plan is None:
+                gtarget, nc = grad, ncell
+            else:                                          # cell gradient on the computational grid first
+                nc = grid.n_cells
+                gtarget = torch.zeros(3 * nc, dtype=torch.float64, device=dev)
+            _lib.check(L.emg3d_dev_edges_to_cells(nx, ny, nz, is_complex, _ptr(t), _ptr(t, o1), _ptr(t, o2), smu0.real,
+                                                  smu0.imag, _ptr(vol), _ptr(gtarget), _ptr(gtarget, nc),
+                                                  _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_edges_to_cells')
+            if plan is not None:                           # ... and back to the model grid: grad += P^T g
+                for k in range(3):
+                    plan.adjoint_add(gtarget[k * nc:(k + 1) * nc], grad[k * ncell:(k + 1) * ncell])
+        return self._gradient_on_host(grad)
+
+    def misfit_and_gradient(self, observed, weights=None):
+        """Misfit ``sum w |synthetic - observed|^2 / 2`` from the kept responses and its gradient
+        ``jtvec((synthetic - observed) w)``."""
+        synthetic = self.synthetic
+        misfit, data = 0.0, {}
+        for i in self._order:
+            pair = self.pairs[i]
+            obs = np.asarray(observed[pair])
+            w = np.ones(obs.shape) if weights is None else np.asarray(weights[pair], dtype=float)
+            residual = synthetic[pair] - obs
+            have = ~np.isnan(residual)
+            misfit += float(np.sum(w[have] * (residual[have].conj() * residual[have])).real) / 2
+            data[pair] = residual * w
+        return misfit, self.jtvec(data)
 
 
 def jvec(model, vector, sources, frequencies, receivers, **kwargs):

@@ -416,6 +416,45 @@ int emg3d_dev_sensitivity_source(int nx, int ny, int nz, int is_complex, const v
                                  const double *vx, const double *vy, const double *vz, void *gx, void *gy,
                                  void *gz, void *stream);
 
+/* ---- solve-free sensitivity products from kept source AND receiver fields --------
+ * The system matrix is complex symmetric and the receiver operator does not depend on the source, so
+ * with one kept field per source, e_s, and one per receiver, x_r = A^-1 (the residual source of a unit
+ * datum at receiver r alone), both products of gradient.ReciprocalSensitivity are reductions over the
+ * kept fields:
+ *     jvec(v)_{s,r} = c sum_k w_k e_s[k] x_r[k]          w = emg3d_dev_edge_weights(v), c = conj(-s mu0)
+ *     jtvec(y)      = edges_to_cells(t),                  t[k] = sum_s e_s[k] sum_r conj(y_{s,r}) x_r[k]
+ * Fields of one kind are STACKED like emg3d_level::batch: field i starts i * stride elements behind
+ * field 0, stride >= n (what lies between n and stride is never read); elements are complex128
+ * (is_complex) or float64. Plain fp64, no atomics, every sum in a fixed order that depends on the sizes
+ * alone: the same call gives the same bits.
+ *
+ * emg3d_dev_edge_weights: emg3d_dev_sensitivity_source without the field,
+ *     w = 1/4 * sum over the (up to four) cells that share the edge of volumes * v,
+ * WRITTEN to w* (laid out like a real field); cells in the same order, vy / vz may alias vx. */
+int emg3d_dev_edge_weights(int nx, int ny, int nz, const double *volumes, const double *vx,
+                           const double *vy, const double *vz, double *wx, double *wy, double *wz,
+                           void *stream);
+/* out[s * nr + r] = scale * sum_k w[k] e_s[k] x_r[k] (out: device, ns * nr elements, written). A
+ * tall-skinny GEMM with K = n, bound by HBM: workgroups stream 8192 consecutive k for a 4 x 4 tile of
+ * (s, r) with the accumulators in registers, reduce in the wave, through LDS, and across workgroups
+ * through ws (doubles, at least emg3d_sensitivity_dots_ws_len(ns, nr, n) of them) in a second launch.
+ * Fields read: e ceil(nr / 4) times, x ceil(ns / 4) times. ns, nr >= 1, otherwise unbounded. */
+size_t emg3d_sensitivity_dots_ws_len(int ns, int nr, size_t n);
+int emg3d_dev_sensitivity_dots(size_t n, int is_complex, const void *e, size_t e_stride, int ns,
+                               const void *x, size_t x_stride, int nr, const double *w, double scale_re,
+                               double scale_im, void *out, double *ws, size_t ws_len, void *stream);
+/* t[k] = sum_s e_s[k] * (sum_r coef[s * nr + r] * x_r[k]), r first, then s, both ascending; t (n
+ * elements) is WRITTEN. coef: device, ns * nr elements of the fields' type. One pass: every e_s once,
+ * every x_r once (beyond 8 receivers the further ones once per source). */
+int emg3d_dev_sensitivity_combine(size_t n, int is_complex, const void *e, size_t e_stride, int ns,
+                                  const void *x, size_t x_stride, int nr, const void *coef, void *t,
+                                  void *stream);
+/* emg3d_dev_gradient_accumulate with the edge product t = b * e already formed:
+ * g += volume / 4 * sum real(s mu0 * t) over a cell's four x-, y- and z-edges, in the same order. */
+int emg3d_dev_edges_to_cells(int nx, int ny, int nz, int is_complex, const void *tx, const void *ty,
+                             const void *tz, double smu0_re, double smu0_im, const double *volumes,
+                             double *gx, double *gy, double *gz, void *stream);
+
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid
  * (emg3d/models.py:322-366). values (nx,ny,nz) -> out (mx,my,mz), doubles, x fastest. Per axis

@@ -1,9 +1,14 @@
 """Wall time of a Gauss-Newton inner iteration -- one ``jvec`` + one ``jtvec`` over K sources x 1 frequency of a bench
-workload -- on one GPU, three ways: forward fields recomputed by every call (``keep=False``: the cost structure of
-``misfit_and_gradient``), kept in HBM (``keep='device'``), and kept with the K right-hand sides solved together
-(``keep='device', batch=K``). Writes profiles/sensitivity_times.txt.
+workload -- on one GPU, four ways: forward fields recomputed by every call (``keep=False``: the cost structure of
+``misfit_and_gradient``), kept in HBM (``keep='device'``), kept with the K right-hand sides solved together
+(``keep='device', batch=K``), and solve-free from kept source and receiver fields (``ReciprocalSensitivity``, row
+``reciprocal``: ``keep='device'``, receiver solves batched by K) with its set-up cost and the number of inner iterations
+after which it has paid for itself. Then the two reductions of the solve-free products alone at the run's sizes
+(HIP events, median of ``--launches`` launches), beside a device-to-device copy of the same byte count and the torch
+composition of the same result, interleaved. Writes profiles/sensitivity_times.txt.
 
-    python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--out profiles/sensitivity_times.txt]
+    python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
+                                     [--out profiles/sensitivity_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -34,11 +39,69 @@ def commit():
         return 'unknown'
 
 
+def kernel_block(rec, say, launches):
+    """``emg3d_dev_sensitivity_dots`` and ``emg3d_dev_sensitivity_combine`` alone on the kept fields of ``rec``."""
+    from emg3d_amd import _lib
+    from emg3d_amd._device import _ptr, _stream
+    L = _lib.lib()
+    (E, X), = rec._stacks.values()
+    ns, nr, n = len(E), len(X), E.shape[1]
+    dev = E.device
+    gen = torch.Generator(device=dev).manual_seed(0)
+    w = torch.randn(n, dtype=torch.float64, device=dev, generator=gen)
+    C = torch.randn(ns, nr, dtype=torch.complex128, device=dev, generator=gen)
+    ws_len = L.emg3d_sensitivity_dots_ws_len(ns, nr, n)
+    ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+    out = torch.empty(ns * nr, dtype=torch.complex128, device=dev)
+    t = torch.empty(n, dtype=torch.complex128, device=dev)
+    bytes_dots = (ns + nr) * 16 * n + 8 * n                  # every field and w read once
+    bytes_comb = (ns + nr) * 16 * n + 16 * n                 # every field read once, t written
+    src = {b: torch.empty(b // 2, dtype=torch.uint8, device=dev) for b in (bytes_dots, bytes_comb)}
+    dst = {b: torch.empty_like(a) for b, a in src.items()}
+
+    def k_dots():
+        _lib.check(L.emg3d_dev_sensitivity_dots(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(w), 0.5, -1.5,
+                                                _ptr(out), _ptr(ws), ws_len, _stream()), 'emg3d_dev_sensitivity_dots')
+
+    def k_comb():
+        _lib.check(L.emg3d_dev_sensitivity_combine(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(C), _ptr(t),
+                                                   _stream()), 'emg3d_dev_sensitivity_combine')
+    what = [('dots: kernel', k_dots, bytes_dots),
+            ('dots: torch (E * w) @ X.T', lambda: (E * w) @ X.T * (0.5 - 1.5j), bytes_dots),
+            ('dots: copy', lambda: dst[bytes_dots].copy_(src[bytes_dots]), bytes_dots),
+            ('combine: kernel', k_comb, bytes_comb),
+            ('combine: torch ((C @ X) * E).sum(0)', lambda: ((C @ X) * E).sum(0), bytes_comb),
+            ('combine: copy', lambda: dst[bytes_comb].copy_(src[bytes_comb]), bytes_comb)]
+    ref_d, ref_c = (E * w) @ X.T * (0.5 - 1.5j), ((C @ X) * E).sum(0)
+    k_dots()
+    k_comb()
+    say(f"kernels alone: n {n:,} edges, ns {ns}, nr {nr}, complex128; algorithmic bytes dots {bytes_dots:,} = (ns + nr) 16 n + "
+        f"8 n, combine {bytes_comb:,} = (ns + nr) 16 n + 16 n; a copy reads half of that count and writes the other half; "
+        f"kernel vs torch, max-norm relative: dots {float((out.view(ns, nr) - ref_d).abs().max() / ref_d.abs().max()):.1e}, "
+        f"combine {float((t - ref_c).abs().max() / ref_c.abs().max()):.1e}")
+    del ref_d, ref_c
+    ms = {name: [] for name, _, _ in what}
+    for rep in range(launches + 3):                  # three warm-up rounds; the candidates take turns
+        for name, fn, _ in what:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if rep >= 3:
+                ms[name].append(a.elapsed_time(b))
+    for name, _, nbytes in what:
+        q = np.percentile(ms[name], [50, 25, 75, 0, 100])
+        say(f"  {name:38s} median {q[0]:8.4f} ms (quartiles {q[1]:.4f} .. {q[2]:.4f}, range {q[3]:.4f} .. {q[4]:.4f}; "
+            f"{len(ms[name])} launches, HIP events) = {nbytes / q[0] / 1e9:7.3f} TB/s on algorithmic bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
+    ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
     args = ap.parse_args()
     K = args.sources
@@ -77,6 +140,18 @@ def main():
         lin.forward()
         t1 = sync()
         say(f"{name:28s} forward(): {1e3 * (t1 - t0):8.1f} ms (the first one builds the hierarchy); {lin!r}")
+        setup = t1 - t0              # (of the last variant, keep='device', batch=K: what `reciprocal` is held against)
+    rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
+                                         batch=K)
+    t0 = sync()
+    rec.forward()
+    t1 = sync()
+    rname = 'reciprocal'
+    say(f"{rname:28s} forward(): {1e3 * (t1 - t0):8.1f} ms = source solves {1e3 * rec.setup_seconds['forward']:8.1f} ms + "
+        f"receiver solves {1e3 * rec.setup_seconds['receiver']:8.1f} ms (it_mg "
+        f"{[rec.info[('receiver', r, 'f')]['it_mg'] for r in range(len(recs))]}); {rec!r}")
+    rec_setup = t1 - t0
+    times[rname] = []
     for r in range(args.repeat + 1):          # run 0: warm-up (coarse levels, line factors, graphs of the batch); the
         for name, _ in variants:              # variants take turns, so that a busy spell of the box hits all of them
             lin = lins[name]
@@ -93,6 +168,17 @@ def main():
                 f"  |jvec| {np.linalg.norm(np.concatenate(list(jv.values()))):.6e} |jtvec| {np.linalg.norm(jt):.6e}")
             if r:
                 times[name].append(t2 - t0)
+        n0 = dict(rec.n_solves)
+        t0 = sync()
+        jv = rec.jvec(v)
+        t1 = sync()
+        jt = rec.jtvec(y)
+        t2 = sync()
+        say(f"{rname:28s} run {r}{' (warm-up)' if r == 0 else '':10s}: jvec {1e3 * (t1 - t0):8.3f}  jtvec "
+            f"{1e3 * (t2 - t1):8.3f}  iteration {1e3 * (t2 - t0):8.3f} ms  solves { {k: rec.n_solves[k] - n0[k] for k in n0} }"
+            f"  |jvec| {np.linalg.norm(np.concatenate(list(jv.values()))):.6e} |jtvec| {np.linalg.norm(jt):.6e}")
+        if r:
+            times[rname].append(t2 - t0)
     mean = {name: float(np.mean(t)) for name, t in times.items()}
     best = {name: float(np.min(t)) for name, t in times.items()}
     for lin in lins.values():
@@ -100,9 +186,16 @@ def main():
     first, kept = "keep=False", "keep='device'"
     for name, t in mean.items():
         b = best[name]
-        say(f"mean of {args.repeat}: {name:28s} {1e3 * t:8.1f} ms per inner iteration = {t / mean[first]:.3f} x keep=False, "
-            f"{t / mean[kept]:.3f} x keep='device'  (fastest run {1e3 * b:8.1f} ms = {b / best[first]:.3f} x, "
-            f"{b / best[kept]:.3f} x)")
+        say(f"mean of {args.repeat}: {name:28s} {1e3 * t:8.2f} ms per inner iteration = {t / mean[first]:.4f} x keep=False, "
+            f"{t / mean[kept]:.4f} x keep='device'  (fastest run {1e3 * b:8.2f} ms = {b / best[first]:.4f} x, "
+            f"{b / best[kept]:.4f} x)")
+    batched = f"keep='device', batch={K}"
+    saving = mean[batched] - mean[rname]
+    say(f"{rname}: set-up {1e3 * rec_setup:.1f} ms against {1e3 * setup:.1f} ms of {batched}: {1e3 * (rec_setup - setup):.1f} ms "
+        f"more; inner iteration {1e3 * mean[rname]:.3f} ms against {1e3 * mean[batched]:.1f} ms: {1e3 * saving:.1f} ms less; "
+        f"break-even after {(rec_setup - setup) / saving:.2f} inner iterations; kept {rec.kept_bytes:,} B")
+    kernel_block(rec, say, args.launches)
+    rec.release()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
         f.write('\n'.join(lines) + '\n')
