@@ -2833,3 +2833,4 @@ int emg3d_core_solve(void *amat, void *bvec, int n, int is_complex)
 #include "krylov.h"
 #include "adjoint.h"
 #include "reciprocal.h"
+#include "hessian.h"

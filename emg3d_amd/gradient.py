@@ -584,7 +584,11 @@ class ReciprocalSensitivity(Sensitivity):
     share ONE computational grid (with a grid per source the receiver fields are not shared); one process only.
     ``n_solves``: ``{'forward', 'receiver', 'jvec', 'jtvec'}``, the last two stay 0. The solver infos of the receiver
     solves: ``info[('receiver', r, frequency name)]``; ``setup_seconds``: wall time ``forward()`` spent in the source
-    and in the receiver solves."""
+    and in the receiver solves.
+
+    From the same kept fields, again without a solve: ``hessian_diagonal``, the diagonal of the Gauss-Newton Hessian
+    ``Re(J^H W J)`` in one pass (``emg3d_dev_hessian_diagonal``), and ``hessian_vec``, the product it
+    preconditions."""
 
     def __init__(self, model, sources, frequencies, receivers, solver_opts=None, tol_gradient=1e-5, costs=None,
                  grids=None, interpolate_opts=None, magnetic=None, keep='device', batch=1):
@@ -750,8 +754,7 @@ class ReciprocalSensitivity(Sensitivity):
     def _gradient_on_host(self, grad):
         """``Sensitivity._gradient_on_host`` with the bookkeeping of ``_finish_gradient`` (same order) on the device:
         only the model's own components cross to the host, laid out as the result."""
-        import torch
-        case, shape = self.model.case, tuple(self.model.grid.shape_cells)
+        case = self.model.case
         g = grad.view(3, -1)
         d = self._chain_factors(grad.device)
         rows = [g[0]]
@@ -764,10 +767,16 @@ class ReciprocalSensitivity(Sensitivity):
         else:
             rows[0] = rows[0] + g[2]
         rows[0] = rows[0] * d[0]
+        return self._rows_on_host(rows)
+
+    def _rows_on_host(self, rows):
+        """One device row of n_cells (x fastest) per property of the model as the model-shaped host array."""
+        import torch
+        shape = tuple(self.model.grid.shape_cells)
         if len(rows) == 1:
             return rows[0].cpu().numpy().reshape(shape, order='F')
         # (n_cells, n) in memory = component fastest, then x: the Fortran order of the (n, nx, ny, nz) result
-        return torch.stack(rows, dim=1).cpu().numpy().reshape(-1).reshape((len(rows),) + shape, order='F')
+        return torch.stack(list(rows), dim=1).cpu().numpy().reshape(-1).reshape((len(rows),) + shape, order='F')
 
     def _per_frequency(self):
         """(frequency name, pair indices, grid key, grid, cell volumes, averaging plan, s mu0) per frequency."""
@@ -878,6 +887,68 @@ class ReciprocalSensitivity(Sensitivity):
             misfit += float(np.sum(w[have] * (residual[have].conj() * residual[have])).real) / 2
             data[pair] = residual * w
         return misfit, self.jtvec(data)
+
+    # ------------------------------------------------------------- Gauss-Newton Hessian ---
+    def _check_weights(self, weights):
+        """The data weights of ``misfit_and_gradient`` as dict pair -> (n_receivers,) floats for every pair: NaN or a
+        missing pair count as 0, ``None`` as all ones; raises unless every entry is real, >= 0 and has one value per
+        receiver."""
+        nrec = len(self._rec[0])
+        if weights is None:
+            return {pair: np.ones(nrec) for pair in self.pairs}
+        for pair, w in weights.items():
+            if np.shape(w) != (nrec,):
+                raise ValueError(f"`weights[{pair!r}]` must have shape ({nrec},): one value per receiver. "
+                                 f"Provided: {np.shape(w)}.")
+            if np.iscomplexobj(w) or np.any(np.asarray(w) < 0):
+                raise ValueError(f"`weights[{pair!r}]` must be real and >= 0 (NaN: no datum). Provided: "
+                                 f"{np.asarray(w).dtype} with minimum {np.nanmin(np.real(w))}.")
+        return {pair: np.nan_to_num(np.asarray(weights[pair], dtype=float), nan=0.0) if pair in weights
+                else np.zeros(nrec) for pair in self.pairs}
+
+    def hessian_diagonal(self, weights=None):
+        """Diagonal of the Gauss-Newton Hessian of the misfit ``sum w |r|^2 / 2``, ``diag Re(J^H W J)[c] = sum_i w_i
+        |J_ic|^2`` -- the Jacobi preconditioner of a Gauss-Newton inner iteration, the pseudo-Hessian of a model update
+        --, shaped and ordered like the result of ``jtvec``. ``weights``: dict (src, freq) -> real array (n_receivers)
+        >= 0, as for ``misfit_and_gradient`` (NaN or a missing pair: 0; ``None``: all ones). Without a solve: per
+        frequency one ``emg3d_dev_hessian_diagonal`` over the kept fields (a frequency whose weights are all zero is
+        skipped). Every computational grid must be the model grid."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        w = self._check_weights(weights)                        # raises before any GPU work
+        mgrid = self.model.grid
+        for pair in self.pairs:
+            g = self.grids.get(pair) if isinstance(self.grids, dict) else self.grids
+            if not (g is None or g == mgrid):
+                raise NotImplementedError(
+                    f"hessian_diagonal: the computational grid of {pair!r} (`grids`) is not the model grid; there every "
+                    "row of the sensitivity needs its own adjoint volume average before the modulus is taken.")
+        dev = self._device()
+        self.forward()
+        rx, ry, rz = _EXPAND[self.model.case]
+        nrows, ncell = _NCOMP[self.model.case], mgrid.n_cells
+        nx, ny, nz = mgrid.shape_cells
+        h = torch.zeros(nrows * ncell, dtype=torch.float64, device=dev)
+        for fname, mine, gkey, grid, vol, plan, smu0 in self._per_frequency():
+            wf = np.stack([w[self.pairs[i]] for i in mine])
+            if not wf.any():
+                continue
+            estack, xstack = self._fields_of(fname)
+            wdev = torch.from_numpy(np.ascontiguousarray(wf)).to(dev)
+            _lib.check(_lib.lib().emg3d_dev_hessian_diagonal(
+                nx, ny, nz, int(estack.dtype == torch.complex128), _ptr(estack), estack.stride(0), len(estack),
+                _ptr(xstack), xstack.stride(0), len(xstack), _ptr(wdev), rx, ry, rz, abs(smu0) ** 2, _ptr(vol), _ptr(h),
+                ncell, _stream()), 'emg3d_dev_hessian_diagonal')
+        d = self._chain_factors(dev)
+        return self._rows_on_host(list(h.view(nrows, ncell) * (d * d)))
+
+    def hessian_vec(self, vector, weights=None):
+        """Gauss-Newton Hessian times a model-shaped real ``vector``: ``jtvec({pair: weights[pair] * jvec(vector)[pair]})``,
+        the product that ``hessian_diagonal`` preconditions, with its conventions for ``weights``."""
+        w = self._check_weights(weights)                        # raises before any GPU work, as jvec does for `vector`
+        jv = self.jvec(vector)
+        return self.jtvec({pair: w[pair] * jv[pair] for pair in jv})
 
 
 def jvec(model, vector, sources, frequencies, receivers, **kwargs):

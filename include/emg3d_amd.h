@@ -454,6 +454,23 @@ int emg3d_dev_sensitivity_combine(size_t n, int is_complex, const void *e, size_
 int emg3d_dev_edges_to_cells(int nx, int ny, int nz, int is_complex, const void *tx, const void *ty,
                              const void *tz, double smu0_re, double smu0_im, const double *volumes,
                              double *gx, double *gy, double *gz, void *stream);
+/* Diagonal of the Gauss-Newton Hessian, diag Re(J^H W J), from the same kept stacks:
+ * the Jacobian row of datum (s, r) w.r.t. the conductivity component d of cell c is
+ * s mu0 V_c / 4 Z_{s,r,d}(c), Z = sum of e_s[k] x_r[k] over the four d-edges of c (those of
+ * emg3d_dev_edges_to_cells, in its order), so
+ *     h[p * h_stride + c] += scale (V_c / 4)^2 sum_{s,r} weights[s * nr + r]
+ *                                               | sum_{d: row_d = p} Z_{s,r,d}(c) |^2 ,
+ * components with the same row added BEFORE the modulus (isotropic (0,0,0), HTI (0,1,0), VTI (0,0,1),
+ * tri-axial (0,1,2)); scale = |s mu0|^2. e, x: stacks as above, every field [x-edges | y-edges |
+ * z-edges], strides >= n_edges; weights: device, ns * nr doubles >= 0; h: rows 0..max(row) of n_cells
+ * doubles (x fastest), h_stride >= n_cells apart, ACCUMULATED into -- rows that no direction maps to
+ * are not touched. One pass: a workgroup stages the edges of a patch of cells for a tile of sources
+ * and receivers in LDS and keeps the tile's pair sums and the three row sums of its cells in registers
+ * (csrc/hessian.h). Plain fp64, no atomics, sums in an order fixed by the sizes. */
+int emg3d_dev_hessian_diagonal(int nx, int ny, int nz, int is_complex, const void *e, size_t e_stride,
+                               int ns, const void *x, size_t x_stride, int nr, const double *weights,
+                               int row_x, int row_y, int row_z, double scale, const double *volumes,
+                               double *h, size_t h_stride, void *stream);
 
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid

@@ -5,10 +5,14 @@ workload -- on one GPU, four ways: forward fields recomputed by every call (``ke
 ``reciprocal``: ``keep='device'``, receiver solves batched by K) with its set-up cost and the number of inner iterations
 after which it has paid for itself. Then the two reductions of the solve-free products alone at the run's sizes
 (HIP events, median of ``--launches`` launches), beside a device-to-device copy of the same byte count and the torch
-composition of the same result, interleaved. Writes profiles/sensitivity_times.txt.
+composition of the same result, interleaved. Writes profiles/sensitivity_times.txt. Last leg: the diagonal of the
+Gauss-Newton Hessian, ``ReciprocalSensitivity.hessian_diagonal`` (one pass over the kept fields), against the row-by-row
+route through the existing ``jtvec`` -- 2 ns nr calls, squared and added --, taking turns, and its kernel alone beside a
+copy of its byte count. Writes profiles/hessian_diagonal_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
-                                     [--out profiles/sensitivity_times.txt]
+                                     [--leg all|products|hessian] [--out profiles/sensitivity_times.txt]
+                                     [--hessian-out profiles/hessian_diagonal_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -96,13 +100,98 @@ def kernel_block(rec, say, launches):
             f"{len(ms[name])} launches, HIP events) = {nbytes / q[0] / 1e9:7.3f} TB/s on algorithmic bytes")
 
 
+def hessian_block(rec, say, repeat, launches):
+    """``hessian_diagonal`` against 2 ns nr calls of ``jtvec`` (unit datum and 1j times it per source, receiver and
+    frequency; squared and added), all weights one; then ``emg3d_dev_hessian_diagonal`` alone on the kept fields."""
+    from emg3d_amd import _lib
+    from emg3d_amd._device import _ptr, _stream
+    nrec = len(rec._rec[0])
+
+    def sync():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def row_by_row():
+        out, calls = 0.0, 0
+        for pair in rec.pairs:
+            for r in range(nrec):
+                unit = np.zeros(nrec, dtype=complex)
+                unit[r] = 1.0
+                for y in (unit, 1j * unit):
+                    out = out + rec.jtvec({pair: y}) ** 2
+                    calls += 1
+        return out, calls
+    times = {'one pass': [], 'row by row': []}
+    for r in range(repeat + 1):                     # run 0: warm-up; the two routes take turns
+        n0 = dict(rec.n_solves)
+        t0 = sync()
+        H = rec.hessian_diagonal()
+        t1 = sync()
+        R, calls = row_by_row()
+        t2 = sync()
+        say(f"run {r}{' (warm-up)' if r == 0 else '':10s}: hessian_diagonal {1e3 * (t1 - t0):9.3f} ms   row by row ({calls} jtvec) "
+            f"{1e3 * (t2 - t1):9.3f} ms   ratio {(t2 - t1) / (t1 - t0):7.1f}   solves { {k: rec.n_solves[k] - n0[k] for k in n0} }"
+            f"   max |H - rows| / max H {float(np.max(np.abs(H - R)) / np.max(H)):.2e}   |H| {np.linalg.norm(H):.6e}")
+        if r:
+            times['one pass'].append(t1 - t0)
+            times['row by row'].append(t2 - t1)
+    one, rows = (float(np.mean(times[k])) for k in ('one pass', 'row by row'))
+    say(f"mean of {repeat}: hessian_diagonal {1e3 * one:.3f} ms, row by row {1e3 * rows:.3f} ms: ratio {rows / one:.1f} "
+        f"(fastest runs {1e3 * min(times['one pass']):.3f} ms, {1e3 * min(times['row by row']):.3f} ms: "
+        f"{min(times['row by row']) / min(times['one pass']):.1f})")
+    del H, R
+    # the kernel alone
+    L = _lib.lib()
+    (E, X), = rec._stacks.values()
+    ns, nr, n = len(E), len(X), E.shape[1]
+    grid = rec.model.grid
+    nx, ny, nz = grid.shape_cells
+    ncell = grid.n_cells
+    rows3 = gradient._EXPAND[rec.model.case]
+    nrows = max(rows3) + 1
+    dev = E.device
+    vol = rec._computational(rec.pairs[0])[3]
+    w = torch.ones(ns * nr, dtype=torch.float64, device=dev)
+    h = torch.zeros(nrows * ncell, dtype=torch.float64, device=dev)
+    nbytes = (ns + nr) * 16 * n + 8 * ncell + 16 * nrows * ncell        # every field once, volumes, h read and written
+    src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+
+    def kernel():
+        _lib.check(L.emg3d_dev_hessian_diagonal(nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(w),
+                                                *rows3, 1.0, _ptr(vol), _ptr(h), ncell, _stream()),
+                   'emg3d_dev_hessian_diagonal')
+    what = [('hessian_diagonal: kernel', kernel), ('hessian_diagonal: copy', lambda: dst.copy_(src))]
+    ms = {name: [] for name, _ in what}
+    for rep in range(launches + 3):                  # three warm-up rounds; the candidates take turns
+        for name, fn in what:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if rep >= 3:
+                ms[name].append(a.elapsed_time(b))
+    say(f"kernel alone: {nx} x {ny} x {nz} cells, n {n:,} edges, ns {ns}, nr {nr}, complex128, rows {rows3}; algorithmic bytes "
+        f"{nbytes:,} = (ns + nr) 16 n + 8 n_cells + 16 rows n_cells; fp64 FMA ~ 55 ns nr n_cells = {55 * ns * nr * ncell:,}; a copy "
+        "reads half of that count and writes the other half")
+    for name, _ in what:
+        q = np.percentile(ms[name], [50, 25, 75, 0, 100])
+        say(f"  {name:28s} median {q[0]:8.4f} ms (quartiles {q[1]:.4f} .. {q[2]:.4f}, range {q[3]:.4f} .. {q[4]:.4f}; "
+            f"{len(ms[name])} launches, HIP events) = {nbytes / q[0] / 1e9:7.3f} TB/s on algorithmic bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
+    ap.add_argument('--leg', choices=('all', 'products', 'hessian'), default='all',
+                    help="products: the inner iteration four ways and its two reductions; hessian: hessian_diagonal against "
+                         "the row-by-row route (needs only the set-up of ReciprocalSensitivity)")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
+    ap.add_argument('--hessian-out', default=os.path.join(ROOT, 'profiles', 'hessian_diagonal_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -117,7 +206,7 @@ def main():
     ncomp = {'isotropic': 1, 'VTI': 2, 'HTI': 2, 'triaxial': 3}[wl['case']]
     v = rng.standard_normal((ncomp,) + tuple(grid.shape_cells))
     y = {(s, 'f'): rng.standard_normal(len(recs)) + 1j * rng.standard_normal(len(recs)) for s in sources}
-    lines = [f"# python tools/sensitivity_time.py --workload {args.workload} --sources {K} --repeat {args.repeat}; box "
+    lines = [f"# python tools/sensitivity_time.py --workload {args.workload} --sources {K} --repeat {args.repeat} --leg {args.leg}; box "
              f"{socket.gethostname()}, {torch.cuda.get_device_name(0)}; commit {commit()}, csrc_sha16 {csrc_sha16()}; "
              f"{time.strftime('%Y-%m-%d')}",
              f"# {wl['label']}; {K} sources x 1 frequency, {len(recs)} receivers; tol 1e-6, tol_gradient 1e-5, "
@@ -131,6 +220,23 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter()
 
+    def hessian_leg(rec):
+        head = [lines[0], f"# {wl['label']}; {K} sources x 1 frequency, {len(recs)} receivers; diag Re(J^H J) from the kept "
+                          f"fields ({rec.kept_bytes:,} B), all weights one; times in ms, synchronised, results on the host"]
+        first = len(lines)
+        hessian_block(rec, say, args.repeat, args.launches)
+        os.makedirs(os.path.dirname(os.path.abspath(args.hessian_out)), exist_ok=True)
+        with open(args.hessian_out, 'w') as f:
+            f.write('\n'.join(head + lines[first:]) + '\n')
+        del lines[first:]
+
+    if args.leg == 'hessian':
+        rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
+                                             batch=K)
+        rec.forward()
+        hessian_leg(rec)
+        rec.release()
+        return
     variants = (("keep=False", dict(keep=False)), ("keep='device'", dict(keep='device')),
                 (f"keep='device', batch={K}", dict(keep='device', batch=K)))
     lins, times = {}, {name: [] for name, _ in variants}
@@ -195,6 +301,8 @@ def main():
         f"more; inner iteration {1e3 * mean[rname]:.3f} ms against {1e3 * mean[batched]:.1f} ms: {1e3 * saving:.1f} ms less; "
         f"break-even after {(rec_setup - setup) / saving:.2f} inner iterations; kept {rec.kept_bytes:,} B")
     kernel_block(rec, say, args.launches)
+    if args.leg == 'all':
+        hessian_leg(rec)
     rec.release()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
