@@ -76,6 +76,11 @@ __global__ __launch_bounds__(KRY_BLOCK) void k_kry_update(KryArgs A, size_t n, c
         }
     }
     if (A.ndots == 0) return;
+    // conj(a) . a is real. The imaginary part of a term, a.re * a.im - a.im * a.re, is contracted to fma(a.re, a.im,
+    // -(a.im * a.re)): the rounding error of the product, not 0. The scalar programs divide by such a dot as it is.
+#pragma unroll
+    for (int k = 0; k < KRY_MAX_DOTS; ++k)
+        if (k < A.ndots && A.da[k] == A.db[k]) acc[k][1] = 0.0;
     __shared__ double sm[KRY_BLOCK / 64][KRY_MAX_DOTS][2];
 #pragma unroll
     for (int k = 0; k < KRY_MAX_DOTS; ++k)

@@ -2249,9 +2249,15 @@ def test_failed_krylov_leaves_a_provided_start_field_alone():
     assert info['exit'] == 1 and not np.any(e.field)
 
 
-@pytest.mark.parametrize('method', ['bicgstab', 'cgs', 'gcrotmk', 'gcrotmk(1,1)'])
-@pytest.mark.parametrize('dtype', [complex, float])
-def test_device_krylov_matches_scipy_iteration(method, dtype, monkeypatch):
+# every method and dtype on 24 x 16 x 20 cells, and BiCGSTAB on 64 x 56 x 52: 578 924 edges, more than the 524 288 entries
+# that one trip of the Krylov kernels' capped grid covers (csrc/krylov.h: 2048 workgroups of 256)
+_KRYLOV_CASES = [pytest.param(method, dtype, (24, 16, 20), id=f'{dtype.__name__}-{method}') for dtype in (complex, float)
+                 for method in ('bicgstab', 'cgs', 'gcrotmk', 'gcrotmk(1,1)')]
+_KRYLOV_CASES.append(pytest.param('bicgstab', complex, (64, 56, 52), id='complex-bicgstab-64x56x52'))
+
+
+@pytest.mark.parametrize('method, dtype, shape', _KRYLOV_CASES)
+def test_device_krylov_matches_scipy_iteration(method, dtype, shape, monkeypatch):
     """The device BiCGSTAB / CGS / GCROT(m,k) (csrc/krylov.h: fused updates + inner products, scalars
     in a device table) against scipy.sparse.linalg's own iteration driven with the same device operator and
     multigrid preconditioner through host vectors: same status, same number of iterations and
@@ -2266,7 +2272,6 @@ def test_device_krylov_matches_scipy_iteration(method, dtype, monkeypatch):
         method, sopts = 'gcrotmk', dict(m=1, k=1)
         monkeypatch.setattr(_krylov, 'gcrotmk', functools.partial(_krylov.gcrotmk, **sopts))
     rng = np.random.default_rng(5)
-    shape = (24, 16, 20)
     h = [widths(n // 2, n // 4, 20., 1.2) for n in shape]
     grid = emg3d.TensorMesh(h, [-w.sum() / 2 for w in h])
     rho = 10 ** rng.uniform(-0.5, 1.0, shape)
