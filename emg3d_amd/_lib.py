@@ -13,7 +13,7 @@ LIBDIR = os.path.join(_HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libemg3d_amd.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'emg3d_amd.h')
 SOURCES = [os.path.join(CSRC, f) for f in ('kernels.hip', 'stencil.h', 'launch.h', 'cplx.h', 'receivers.h', 'krylov.h',
-                                            'adjoint.h', 'reciprocal.h', 'hessian.h')] + [HEADER]
+                                            'adjoint.h', 'reciprocal.h', 'hessian.h', 'gram.h')] + [HEADER]
 
 # -ffp-contract: hipcc's own default for HIP, spelled out because csrc/kernels.hip switches contraction off for its
 # line-kernel section and back to THIS mode behind it (`#pragma clang fp contract(fast)`: the pragma can name a mode,
@@ -105,6 +105,10 @@ SIGNATURES = {
     'emg3d_dev_edges_to_cells': (_ci, [_ci] * 4 + [_vp] * 3 + [ctypes.c_double] * 2 + [_vp] * 4 + [_vp]),
     'emg3d_dev_hessian_diagonal': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci, _vp] + [_ci] * 3 + [ctypes.c_double] +
                                    [_vp, _vp, _sz, _vp]),
+    'emg3d_data_gram_ws_len': (_sz, [_ci] * 6),
+    'emg3d_dev_data_gram': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 +
+                            [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 + [_ci] * 3 +
+                            [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
     'emg3d_dev_source_field': (_ci, [_ci] * 4 + [_vp] * 7 + [_ci] + [ctypes.c_double] * 2 + [_vp] * 4),
     'emg3d_dev_volume_model': (_ci, [_ci] * 4 + [_vp] * 5 + [_ci] + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp] * 5),
     'emg3d_dev_magnetic_field': (_ci, [_ci] * 4 + [_vp] * 7 + [ctypes.c_double] * 2 + [_vp] * 4),

@@ -2834,3 +2834,4 @@ int emg3d_core_solve(void *amat, void *bvec, int n, int is_complex)
 #include "adjoint.h"
 #include "reciprocal.h"
 #include "hessian.h"
+#include "gram.h"

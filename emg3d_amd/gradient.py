@@ -588,7 +588,9 @@ class ReciprocalSensitivity(Sensitivity):
 
     From the same kept fields, again without a solve: ``hessian_diagonal``, the diagonal of the Gauss-Newton Hessian
     ``Re(J^H W J)`` in one pass (``emg3d_dev_hessian_diagonal``), and ``hessian_vec``, the product it
-    preconditions."""
+    preconditions; and ``data_gram``, the data-space normal matrix ``J^ diag(m) J^T`` of Occam and data-space
+    Gauss-Newton schemes (``emg3d_dev_data_gram``, DESIGN.md 4.14: the rows of ``J^`` are generated in LDS and consumed
+    there, never written), with ``stack_data`` / ``unstack_data`` between data dictionaries and its real vectors."""
 
     def __init__(self, model, sources, frequencies, receivers, solver_opts=None, tol_gradient=1e-5, costs=None,
                  grids=None, interpolate_opts=None, magnetic=None, keep='device', batch=1):
@@ -949,6 +951,138 @@ class ReciprocalSensitivity(Sensitivity):
         w = self._check_weights(weights)                        # raises before any GPU work, as jvec does for `vector`
         jv = self.jvec(vector)
         return self.jtvec({pair: w[pair] * jv[pair] for pair in jv})
+
+    # ------------------------------------------------------- data-space normal matrix ---
+    def _data_rows(self):
+        """Real rows per datum in ``data_gram``: 2 (frequency domain: Re and Im) or 1 (Laplace domain); a survey that
+        mixes the two is refused."""
+        laplace = {float(f) < 0 for f in self.frequencies.values()}
+        if len(laplace) > 1:
+            raise NotImplementedError("data_gram: the survey mixes Laplace- and frequency-domain frequencies; their "
+                                      "kept fields have different types (real and complex).")
+        return 1 if laplace == {True} else 2
+
+    def stack_data(self, data):
+        """The data dictionary ``data`` (pair -> (n_receivers,) values, as ``jtvec`` takes it) as the real vector
+        (M,) in the ordering of ``data_gram``: datum ``i = pair index * n_receivers + receiver`` (pairs as in
+        ``self.pairs``), entry ``i`` its real part and, in the frequency domain, entry ``N + i`` its imaginary part.
+        NaN or a missing pair: 0. Host code: neither a GPU nor ``forward()`` is needed."""
+        nrec, c = self._check_data(data), self._data_rows()
+        n = len(self.pairs) * nrec
+        out = np.zeros(c * n)
+        for i, pair in enumerate(self.pairs):
+            y = data.get(pair)
+            if y is not None:
+                y = np.array(y, dtype=complex)
+                y[np.isnan(y)] = 0.0
+                out[i * nrec:(i + 1) * nrec] = y.real
+                if c == 2:
+                    out[n + i * nrec:n + (i + 1) * nrec] = y.imag
+        return out
+
+    def unstack_data(self, vector):
+        """The inverse of ``stack_data`` on complete data: dict pair -> (n_receivers,) complex values (Laplace
+        domain: real values) of a real vector (M,)."""
+        nrec, c = len(self._rec[0]), self._data_rows()
+        n = len(self.pairs) * nrec
+        v = np.asarray(vector)
+        if v.shape != (c * n,) or np.iscomplexobj(v):
+            raise ValueError(f"`vector` must be real with shape ({c * n},): {c} x {len(self.pairs)} pairs x {nrec} "
+                             f"receivers. Provided: {v.dtype} {v.shape}.")
+        v = np.asarray(v, dtype=np.float64)
+        return {pair: (v[i * nrec:(i + 1) * nrec] + 1j * v[n + i * nrec:n + (i + 1) * nrec] if c == 2
+                       else v[i * nrec:(i + 1) * nrec].copy()) for i, pair in enumerate(self.pairs)}
+
+    def _check_model_weights(self, model_weights):
+        """The model weights of ``data_gram`` as (n, nx, ny, nz) floats (``None``: ones); raises unless they are real,
+        >= 0 and shaped like the vector of ``jvec``."""
+        if model_weights is None:
+            return np.ones((_NCOMP[self.model.case],) + tuple(self.model.grid.shape_cells))
+        try:
+            m = _check_vector(self.model, model_weights)
+        except ValueError as e:
+            raise ValueError(str(e).replace('`vector`', '`model_weights`')) from None
+        if not np.all(m >= 0):
+            raise ValueError(f"`model_weights` must be >= 0. Provided: minimum {np.min(m)}"
+                             f"{', with NaN' if np.isnan(m).any() else ''}.")
+        return m
+
+    def data_gram(self, model_weights=None):
+        """The data-space Gauss-Newton matrix ``J^ diag(model_weights) J^T``: ndarray (M, M) of float64, C-contiguous
+        and exactly symmetric, in the ordering of ``stack_data`` -- ``J^`` has the rows ``Re J_i`` and (frequency
+        domain) ``Im J_i`` of the sensitivity of ``jtvec(y) = sum_i Re(conj(y_i) J_i)``, so for all data y, z
+
+            stack_data(y) @ G @ stack_data(z) == sum(model_weights * jtvec(y) * jtvec(z))
+            G @ stack_data(y)                 == stack_data(jvec(model_weights * jtvec(y)))
+
+        (the second in the frequency domain; in the Laplace domain ``jvec`` is MINUS the adjoint of ``jtvec``, as in the
+        reference, and the right-hand side changes its sign -- the matrix is positive semi-definite in both).
+
+        ``model_weights``: real, >= 0, shaped like the vector of ``jvec`` (``None``: ones). Without a solve and
+        without ever forming ``J^``: one ``emg3d_dev_data_gram`` over the kept fields per unordered pair of
+        frequencies, the transposed block is copied; assembled on the device, downloaded once.
+        ``keep='host'`` holds a second staging pair for the duration of the call when there is more than one
+        frequency. Every computational grid must be the model grid."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        m = self._check_model_weights(model_weights)            # raises before any GPU work
+        mgrid = self.model.grid
+        for pair in self.pairs:
+            g = self.grids.get(pair) if isinstance(self.grids, dict) else self.grids
+            if not (g is None or g == mgrid):
+                raise NotImplementedError(
+                    f"data_gram: the computational grid of {pair!r} (`grids`) is not the model grid; there every row "
+                    "of the sensitivity needs its own adjoint volume average before the product is taken.")
+        c = self._data_rows()
+        dev = self._device()
+        self.forward()
+        L = _lib.lib()
+        rx, ry, rz = _EXPAND[self.model.case]
+        ncell = mgrid.n_cells
+        nx, ny, nz = mgrid.shape_cells
+        nrec = len(self._rec[0])
+        n = len(self.pairs) * nrec
+        d = self._chain_factors(dev)
+        mw = (torch.from_numpy(np.ascontiguousarray(m)).to(dev).permute(0, 3, 2, 1).reshape(len(m), -1) * (d * d)).contiguous()
+        G = torch.zeros((c * n, c * n), dtype=torch.float64, device=dev)
+        per_freq = list(self._per_frequency())
+        # rows of G of a frequency's block: Re of its data (its pairs in the order of its stack), then Im
+        rows = [torch.tensor([part * n + i * nrec + r for part in range(c) for i in mine for r in range(nrec)],
+                             dtype=torch.int64, device=dev) for _, mine, *_ in per_freq]
+        second = None                                           # keep='host': staging pair of the partner frequency
+        try:
+            for a, (fa, mine_a, _, _, vol, _, smu0_a) in enumerate(per_freq):
+                ea, xa = self._fields_of(fa)
+                is_complex = int(ea.dtype == torch.complex128)
+                for b in range(a, len(per_freq)):
+                    fb, mine_b, _, _, _, _, smu0_b = per_freq[b]
+                    if b == a:
+                        eb, xb = ea, xa
+                    elif self.keep == 'device':
+                        eb, xb = self._stacks[fb]
+                    else:
+                        if second is None:
+                            second = [torch.empty_like(buf) for buf in self._stage]
+                        eb, xb = (buf[:host.numel()].view(host.shape) for buf, host in zip(second, self._stacks[fb]))
+                        eb.copy_(self._stacks[fb][0])
+                        xb.copy_(self._stacks[fb][1])
+                    na, nb = len(mine_a) * nrec, len(mine_b) * nrec
+                    ws_len = L.emg3d_data_gram_ws_len(nx, ny, nz, is_complex, na, nb)
+                    ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+                    blk = torch.empty((c * na, c * nb), dtype=torch.float64, device=dev)
+                    _lib.check(L.emg3d_dev_data_gram(
+                        nx, ny, nz, is_complex, _ptr(ea), ea.stride(0), len(ea), _ptr(xa), xa.stride(0), len(xa),
+                        smu0_a.real, smu0_a.imag, _ptr(eb), eb.stride(0), len(eb), _ptr(xb), xb.stride(0), len(xb),
+                        smu0_b.real, smu0_b.imag, rx, ry, rz, _ptr(mw), ncell, _ptr(vol), _ptr(blk), c * nb, _ptr(ws),
+                        ws_len, _stream()), 'emg3d_dev_data_gram')
+                    G[rows[a][:, None], rows[b][None, :]] = blk
+                    if b != a:
+                        G[rows[b][:, None], rows[a][None, :]] = blk.T
+                    del ws, blk
+        finally:
+            del second
+        return G.cpu().numpy()
 
 
 def jvec(model, vector, sources, frequencies, receivers, **kwargs):

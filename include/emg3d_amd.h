@@ -471,6 +471,31 @@ int emg3d_dev_hessian_diagonal(int nx, int ny, int nz, int is_complex, const voi
                                int ns, const void *x, size_t x_stride, int nr, const double *weights,
                                int row_x, int row_y, int row_z, double scale, const double *volumes,
                                double *h, size_t h_stride, void *stream);
+/* One block of the data-space Gauss-Newton matrix G^ = J^ diag(m) J^T between the data
+ * of a side A and a side B -- two frequencies, or one and the same --, from the kept stacks of either
+ * side (conventions as above). J^ has the rows Re J_i, i = s * nr + r, and, for complex fields (c = 2;
+ * real fields: c = 1), behind them the rows Im J_i. out[i * ld + j], i < c ns_a nr_a, j < c ns_b nr_b,
+ * is WRITTEN (entries between a row's end and ld are not touched):
+ *     out[i, j] = sum_{p, cell} mw[p * mw_stride + cell] (V_cell / 4)^2 a^_{i,p}(cell) b^_{j,p}(cell),
+ * a^ = real part (first half of the rows, s-major) or imaginary part (second half) of
+ * scale_a * sum_{d: row_d = p} Z^A_{s,r,d}(cell), b^ the same of side B; Z: the pair sum of
+ * emg3d_dev_hessian_diagonal (same four edges per direction, same order); scale: the frequency's
+ * s mu0 (real fields: scale_re); model_weights: device, rows 0..max(row) of n_cells doubles >= 0,
+ * mw_stride >= n_cells apart, already model weights * chain^2. ws: device,
+ * >= emg3d_data_gram_ws_len(nx, ny, nz, is_complex, ns_a * nr_a, ns_b * nr_b) doubles (0: bad sizes).
+ * Two launches (csrc/gram.h): workgroups that own a pair of 32-datum tiles generate the rows of J^ for
+ * a patch of cells in LDS and consume them in a rank update held in registers; their partial tiles go
+ * to ws and are added in ascending order. Plain fp64, no atomics, every sum in an order fixed by the
+ * sizes alone. With the same stacks, strides, counts and scales on both sides the block is bitwise
+ * symmetric: one triangle of tile pairs is computed and mirrored. */
+size_t emg3d_data_gram_ws_len(int nx, int ny, int nz, int is_complex, int n_a, int n_b);
+int emg3d_dev_data_gram(int nx, int ny, int nz, int is_complex, const void *e_a, size_t e_a_stride,
+                        int ns_a, const void *x_a, size_t x_a_stride, int nr_a, double scale_a_re,
+                        double scale_a_im, const void *e_b, size_t e_b_stride, int ns_b, const void *x_b,
+                        size_t x_b_stride, int nr_b, double scale_b_re, double scale_b_im, int row_x,
+                        int row_y, int row_z, const double *model_weights, size_t mw_stride,
+                        const double *volumes, double *out, size_t ld, double *ws, size_t ws_len,
+                        void *stream);
 
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid

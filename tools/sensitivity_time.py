@@ -8,11 +8,15 @@ after which it has paid for itself. Then the two reductions of the solve-free pr
 composition of the same result, interleaved. Writes profiles/sensitivity_times.txt. Last leg: the diagonal of the
 Gauss-Newton Hessian, ``ReciprocalSensitivity.hessian_diagonal`` (one pass over the kept fields), against the row-by-row
 route through the existing ``jtvec`` -- 2 ns nr calls, squared and added --, taking turns, and its kernel alone beside a
-copy of its byte count. Writes profiles/hessian_diagonal_times.txt.
+copy of its byte count. Writes profiles/hessian_diagonal_times.txt. Leg ``gram``: the data-space normal matrix,
+``ReciprocalSensitivity.data_gram``, against the route through the existing ``jtvec`` -- 2 N calls on unit data and 1j
+times them, stacked, then ``(Jhat * m) @ Jhat.T`` in NumPy --, taking turns, with one frequency and with two; its kernel
+alone beside a copy of its byte count, and the achieved FMA rate. Writes profiles/data_gram_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
-                                     [--leg all|products|hessian] [--out profiles/sensitivity_times.txt]
+                                     [--leg all|products|hessian|gram] [--out profiles/sensitivity_times.txt]
                                      [--hessian-out profiles/hessian_diagonal_times.txt]
+                                     [--gram-out profiles/data_gram_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -181,17 +185,120 @@ def hessian_block(rec, say, repeat, launches):
             f"{len(ms[name])} launches, HIP events) = {nbytes / q[0] / 1e9:7.3f} TB/s on algorithmic bytes")
 
 
+def gram_block(rec, say, repeat, launches, kernel):
+    """``data_gram`` against 2 N calls of ``jtvec`` (unit datum and 1j times it per pair and receiver), stacked, and
+    ``(Jhat * m) @ Jhat.T`` on the host, all model weights one; with ``kernel``: ``emg3d_dev_data_gram`` alone on the
+    kept fields of the (one) frequency."""
+    from emg3d_amd import _lib
+    from emg3d_amd._device import _ptr, _stream
+    nrec, npairs = len(rec._rec[0]), len(rec.pairs)
+    N = npairs * nrec
+
+    def sync():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def route():
+        Jhat, calls = None, 0
+        for k, pair in enumerate(rec.pairs):
+            for r in range(nrec):
+                unit = np.zeros(nrec, dtype=complex)
+                unit[r] = 1.0
+                for half, y in enumerate((unit, 1j * unit)):
+                    row = rec.jtvec({pair: y}).ravel()
+                    if Jhat is None:
+                        Jhat = np.empty((2 * N, row.size))
+                    Jhat[half * N + k * nrec + r] = row
+                    calls += 1
+        t = sync()
+        return Jhat @ Jhat.T, calls, t                   # (m = 1)
+    times = {'data_gram': [], 'route': [], 'calls': []}
+    for r in range(repeat + 1):                     # run 0: warm-up; the two routes take turns
+        n0 = dict(rec.n_solves)
+        t0 = sync()
+        G = rec.data_gram()
+        t1 = sync()
+        R, calls, tj = route()
+        t2 = sync()
+        say(f"run {r}{' (warm-up)' if r == 0 else '':10s}: data_gram {1e3 * (t1 - t0):9.3f} ms   route ({calls} jtvec + product) "
+            f"{1e3 * (t2 - t1):9.3f} ms (jtvec calls {1e3 * (tj - t1):9.3f} ms)   ratio {(t2 - t1) / (t1 - t0):7.1f}   solves "
+            f"{ {k: rec.n_solves[k] - n0[k] for k in n0} }   max |G - route| / max G {float(np.max(np.abs(G - R)) / np.max(G)):.2e}"
+            f"   symmetric {bool(np.array_equal(G, G.T))}   |G| {np.linalg.norm(G):.6e}")
+        if r:
+            times['data_gram'].append(t1 - t0)
+            times['route'].append(t2 - t1)
+            times['calls'].append(tj - t1)
+    one, rows, calls_only = (float(np.mean(times[k])) for k in ('data_gram', 'route', 'calls'))
+    say(f"mean of {repeat}: data_gram {1e3 * one:.3f} ms, route {1e3 * rows:.3f} ms (its jtvec calls alone {1e3 * calls_only:.3f} "
+        f"ms): ratio {rows / one:.1f} (fastest runs {1e3 * min(times['data_gram']):.3f} ms, {1e3 * min(times['route']):.3f} ms: "
+        f"{min(times['route']) / min(times['data_gram']):.1f})")
+    del G, R
+    if not kernel:
+        return
+    L = _lib.lib()
+    (E, X), = rec._stacks.values()
+    ns, nr, n = len(E), len(X), E.shape[1]
+    grid = rec.model.grid
+    nx, ny, nz = grid.shape_cells
+    ncell = grid.n_cells
+    rows3 = gradient._EXPAND[rec.model.case]
+    nrows = max(rows3) + 1
+    dev = E.device
+    vol = rec._computational(rec.pairs[0])[3]
+    mw = torch.ones(nrows * ncell, dtype=torch.float64, device=dev)
+    M = 2 * ns * nr
+    out = torch.empty(M * M, dtype=torch.float64, device=dev)
+    ws_len = L.emg3d_data_gram_ws_len(nx, ny, nz, 1, ns * nr, ns * nr)
+    ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+    nbytes = (ns + nr) * 16 * n + 8 * ncell + 8 * nrows * ncell + 16 * ws_len   # fields, volumes, weights; ws written and read
+    src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+
+    def kernel_call():
+        _lib.check(L.emg3d_dev_data_gram(nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, 0.0, 1e-5, _ptr(E),
+                                         E.stride(0), ns, _ptr(X), X.stride(0), nr, 0.0, 1e-5, *rows3, _ptr(mw), ncell, _ptr(vol),
+                                         _ptr(out), M, _ptr(ws), ws_len, _stream()), 'emg3d_dev_data_gram')
+    what = [('data_gram: kernel (two launches)', kernel_call), ('data_gram: copy', lambda: dst.copy_(src))]
+    ms = {name: [] for name, _ in what}
+    for rep in range(launches + 3):                  # three warm-up rounds; the candidates take turns
+        for name, fn in what:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if rep >= 3:
+                ms[name].append(a.elapsed_time(b))
+    # rows: 4 edges x 4 FMA per complex product and pair and direction (3 directions in all) + the scaling;
+    # update: the full M x M tile per cell and property row (the kernel does not skip the lower triangle)
+    fma_rows, fma_full, fma_tri = 55 * ns * nr * ncell, M * M * nrows * ncell, M * (M + 1) // 2 * nrows * ncell
+    say(f"kernel alone: {nx} x {ny} x {nz} cells, n {n:,} edges, ns {ns}, nr {nr}, complex128, rows {rows3}, M {M}; algorithmic "
+        f"bytes {nbytes:,} = (ns + nr) 16 n + 8 n_cells + 8 rows n_cells + 16 ws_len; fp64 FMA: rows of J ~ 55 ns nr n_cells = "
+        f"{fma_rows:,}, update as issued M^2 rows n_cells = {fma_full:,} (one triangle: {fma_tri:,}); a copy reads half of the "
+        "byte count and writes the other half")
+    for name, _ in what:
+        q = np.percentile(ms[name], [50, 25, 75, 0, 100])
+        say(f"  {name:34s} median {q[0]:8.4f} ms (quartiles {q[1]:.4f} .. {q[2]:.4f}, range {q[3]:.4f} .. {q[4]:.4f}; "
+            f"{len(ms[name])} launches, HIP events) = {nbytes / q[0] / 1e9:7.3f} TB/s on algorithmic bytes")
+    med = float(np.median(ms[what[0][0]]))
+    say(f"  FMA rate of the kernel: issued {(fma_rows + fma_full) / med / 1e9:.2f} T FMA/s = {2 * (fma_rows + fma_full) / med / 1e9:.2f} "
+        f"TFLOP/s fp64; on the count with one triangle {(fma_rows + fma_tri) / med / 1e9:.2f} T FMA/s = "
+        f"{2 * (fma_rows + fma_tri) / med / 1e9:.2f} TFLOP/s")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
-    ap.add_argument('--leg', choices=('all', 'products', 'hessian'), default='all',
+    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram'), default='all',
                     help="products: the inner iteration four ways and its two reductions; hessian: hessian_diagonal against "
-                         "the row-by-row route (needs only the set-up of ReciprocalSensitivity)")
+                         "the row-by-row route (needs only the set-up of ReciprocalSensitivity); gram: data_gram against the "
+                         "route through jtvec, one frequency and two (the same set-up, once per survey)")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
     ap.add_argument('--hessian-out', default=os.path.join(ROOT, 'profiles', 'hessian_diagonal_times.txt'))
+    ap.add_argument('--gram-out', default=os.path.join(ROOT, 'profiles', 'data_gram_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -230,11 +337,31 @@ def main():
             f.write('\n'.join(head + lines[first:]) + '\n')
         del lines[first:]
 
-    if args.leg == 'hessian':
+    def gram_leg(rec):
+        """``rec``: the one-frequency object; the two-frequency one (the second at twice the frequency) is built here."""
+        head = [lines[0], f"# {wl['label']}; {K} sources, {len(recs)} receivers; J^ J^T (all model weights one) from the kept "
+                          "fields; route: 2 N jtvec calls + (Jhat * m) @ Jhat.T in NumPy; times in ms, synchronised, results "
+                          "on the host"]
+        first = len(lines)
+        say(f"one frequency: M = {2 * len(rec.pairs) * len(recs)}, kept {rec.kept_bytes:,} B")
+        gram_block(rec, say, args.repeat, args.launches, kernel=True)
+        two = gradient.ReciprocalSensitivity(model, sources, {'f': wl['frequency'], 'g': 2 * wl['frequency']}, recs,
+                                             solver_opts=dict(wl['opts'], tol=1e-6), keep='device', batch=K)
+        two.forward()
+        say(f"two frequencies ({wl['frequency']} and {2 * wl['frequency']} Hz): M = {2 * len(two.pairs) * len(recs)}, kept "
+            f"{two.kept_bytes:,} B; three kernel calls (f-f, f-g, g-g)")
+        gram_block(two, say, args.repeat, args.launches, kernel=False)
+        two.release()
+        os.makedirs(os.path.dirname(os.path.abspath(args.gram_out)), exist_ok=True)
+        with open(args.gram_out, 'w') as f:
+            f.write('\n'.join(head + lines[first:]) + '\n')
+        del lines[first:]
+
+    if args.leg in ('hessian', 'gram'):
         rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
                                              batch=K)
         rec.forward()
-        hessian_leg(rec)
+        (hessian_leg if args.leg == 'hessian' else gram_leg)(rec)
         rec.release()
         return
     variants = (("keep=False", dict(keep=False)), ("keep='device'", dict(keep='device')),
@@ -303,6 +430,7 @@ def main():
     kernel_block(rec, say, args.launches)
     if args.leg == 'all':
         hessian_leg(rec)
+        gram_leg(rec)
     rec.release()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
