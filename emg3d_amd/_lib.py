@@ -109,6 +109,15 @@ SIGNATURES = {
     'emg3d_dev_data_gram': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 +
                             [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 + [_ci] * 3 +
                             [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
+    # stacks stored as complex64 / float32: the argument lists of the fp64 siblings
+    'emg3d_dev_sensitivity_dots_sp': (_ci, [_sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci, _vp] + [ctypes.c_double] * 2 +
+                                      [_vp, _vp, _sz, _vp]),
+    'emg3d_dev_sensitivity_combine_sp': (_ci, [_sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci, _vp, _vp, _vp]),
+    'emg3d_dev_hessian_diagonal_sp': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci, _vp] + [_ci] * 3 + [ctypes.c_double] +
+                                      [_vp, _vp, _sz, _vp]),
+    'emg3d_dev_data_gram_sp': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 +
+                               [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 + [_ci] * 3 +
+                               [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
     'emg3d_dev_source_field': (_ci, [_ci] * 4 + [_vp] * 7 + [_ci] + [ctypes.c_double] * 2 + [_vp] * 4),
     'emg3d_dev_volume_model': (_ci, [_ci] * 4 + [_vp] * 5 + [_ci] + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp] * 5),
     'emg3d_dev_magnetic_field': (_ci, [_ci] * 4 + [_vp] * 7 + [ctypes.c_double] * 2 + [_vp] * 4),

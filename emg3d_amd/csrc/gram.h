@@ -38,19 +38,22 @@ static_assert(GR_CELLS % GR_WAVES == 0 && GR_DATA == 32, "a wave's share of the 
 template <class T> struct GramRows { static constexpr int R = GR_DATA * (int)(sizeof(T) / sizeof(double)), PS = R + 2; };
 // staging + two panels of PS = R + 2 doubles per cell (the padding spreads a wave's panel writes over the banks);
 // the waves' final sum (R x R) reuses the panels
-template <class T> constexpr size_t gram_lds_bytes()
+// S: the type the stacks are stored in (T, or its single-precision partner). The edges are staged AS STORED and widened
+// when a thread reads them for its pair sums; the panels and everything behind them are fp64 whatever S is.
+template <class T, class S = T> constexpr size_t gram_lds_bytes()
 {
-    return (size_t)GR_FIELDS * GR_EDGES * sizeof(T) + (size_t)2 * GR_CELLS * GramRows<T>::PS * sizeof(double);
+    return (size_t)GR_FIELDS * GR_EDGES * sizeof(S) + (size_t)2 * GR_CELLS * GramRows<T>::PS * sizeof(double);
 }
+static_assert((size_t)GR_FIELDS * GR_EDGES * sizeof(float) % 16 == 0, "the panels start on a 16-byte boundary behind any stage");
 static_assert((size_t)GramRows<cplx>::R * GramRows<cplx>::R <= (size_t)2 * GR_CELLS * GramRows<cplx>::PS, "final sum in the panels");
 static_assert((size_t)GramRows<double>::R * GramRows<double>::R <= (size_t)2 * GR_CELLS * GramRows<double>::PS, "final sum in the panels");
 static_assert(gram_lds_bytes<cplx>() <= (size_t)160 * 1024, "LDS of a compute unit");
 
-template <class T> struct GramSide {
-    const T *e;
+template <class T, class S> struct GramSide {
+    const S *e;
     size_t es;
     int ns;
-    const T *x;
+    const S *x;
     size_t xs;
     int nr;
     T scale;
@@ -63,9 +66,9 @@ __device__ __forceinline__ double gram_im(cplx a) { return a.im; }
 __device__ __forceinline__ double gram_im(double) { return 0.0; }
 
 // Step 1 for one side: the panel rows of tile `tile` for the patch at (x0, y0, z0) and property row p.
-template <class T>
-__device__ __forceinline__ void gram_panel(int nx, int ny, int nz, const GramSide<T> &S, int tile, int x0, int y0, int z0,
-                                           int p, int row_x, int row_y, int row_z, double f, T *__restrict__ stage,
+template <class T, class S>
+__device__ __forceinline__ void gram_panel(int nx, int ny, int nz, const GramSide<T, S> &A, int tile, int x0, int y0, int z0,
+                                           int p, int row_x, int row_y, int row_z, double f, S *__restrict__ stage,
                                            double *__restrict__ panel)
 {
     constexpr int PS = GramRows<T>::PS;
@@ -73,7 +76,7 @@ __device__ __forceinline__ void gram_panel(int nx, int ny, int nz, const GramSid
     const int tx = t % GR_PX, trow = t / GR_PX;             // staging: thread tx of row slot trow
     const int cl = t % GR_CELLS, q = t / GR_CELLS;          // the thread's cell in the patch and its receiver pair
     const int cx = cl % GR_PX, cy = (cl / GR_PX) % GR_PY, cz = cl / (GR_PX * GR_PY);
-    const int s0 = (tile / S.ntr) * GR_TS, r0 = (tile % S.ntr) * GR_TR;
+    const int s0 = (tile / A.ntr) * GR_TS, r0 = (tile % A.ntr) * GR_TR;
     const size_t n_x = (size_t)nx * (ny + 1) * (nz + 1), n_y = (size_t)(nx + 1) * ny * (nz + 1);
     T acc[GR_TS][2];
 #pragma unroll
@@ -90,27 +93,27 @@ __device__ __forceinline__ void gram_panel(int nx, int ny, int nz, const GramSid
         for (int idx = trow; idx < GR_FIELDS * nrows; idx += GR_THREADS / GR_PX) {
             const int fld = idx / nrows, row = idx % nrows;
             const int gj = y0 + row % ly, gk = z0 + row / ly;
-            const bool have = fld < GR_TS ? s0 + fld < S.ns : r0 + (fld - GR_TS) < S.nr;
-            const T *const src = !have ? S.e : fld < GR_TS ? S.e + (size_t)(s0 + fld) * S.es
-                                                             : S.x + (size_t)(r0 + (fld - GR_TS)) * S.xs;
+            const bool have = fld < GR_TS ? s0 + fld < A.ns : r0 + (fld - GR_TS) < A.nr;
+            const S *const src = !have ? A.e : fld < GR_TS ? A.e + (size_t)(s0 + fld) * A.es
+                                                             : A.x + (size_t)(r0 + (fld - GR_TS)) * A.xs;
             for (int li = tx; li < lx; li += GR_PX) {
                 const int gi = x0 + li;
                 const bool in = have && gi < gnx && gj < gny && gk < gnz;
                 const size_t g = goff + gi + (size_t)gnx * (gj + (size_t)gny * gk);
-                stage[fld * GR_EDGES + li + lx * row] = in ? src[g] : emg::zero<T>();
+                stage[fld * GR_EDGES + li + lx * row] = in ? src[g] : emg::narrow<S>(emg::zero<T>());
             }
         }
         __syncthreads();
         // the four d-edges of the cell in the order of edges_to_cell: x: y inner, z outer; y: x, z; z: x, y
         const int o1 = d == 0 ? lx : 1, o2 = d == 2 ? lx : lx * ly;
-        const T *const src = stage + (cx + lx * (cy + ly * cz));
+        const S *const src = stage + (cx + lx * (cy + ly * cz));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const T *const e4 = src + ((k & 1) * o1 + (k >> 1) * o2);
-            const T x0v = e4[(GR_TS + 2 * q) * GR_EDGES], x1v = e4[(GR_TS + 2 * q + 1) * GR_EDGES];
+            const S *const e4 = src + ((k & 1) * o1 + (k >> 1) * o2);
+            const T x0v = emg::widen(e4[(GR_TS + 2 * q) * GR_EDGES]), x1v = emg::widen(e4[(GR_TS + 2 * q + 1) * GR_EDGES]);
 #pragma unroll
             for (int i = 0; i < GR_TS; ++i) {
-                const T ev = e4[i * GR_EDGES];
+                const T ev = emg::widen(e4[i * GR_EDGES]);
                 acc[i][0] = emg::mad(ev, x0v, acc[i][0]);
                 acc[i][1] = emg::mad(ev, x1v, acc[i][1]);
             }
@@ -121,14 +124,14 @@ __device__ __forceinline__ void gram_panel(int nx, int ny, int nz, const GramSid
     for (int i = 0; i < GR_TS; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const T v = S.scale * acc[i][j];
+            const T v = A.scale * acc[i][j];
             dst[i * GR_TR + j] = f * gram_re(v);
             if (sizeof(T) > sizeof(double)) dst[GR_DATA + i * GR_TR + j] = f * gram_im(v);
         }
 }
 
-template <class T>
-__global__ __launch_bounds__(GR_THREADS) void k_data_gram(int nx, int ny, int nz, GramSide<T> A, GramSide<T> B, int n_tiles_b,
+template <class T, class S>
+__global__ __launch_bounds__(GR_THREADS) void k_data_gram(int nx, int ny, int nz, GramSide<T, S> A, GramSide<T, S> B, int n_tiles_b,
                                                           int same, int row_x, int row_y, int row_z,
                                                           const double *__restrict__ mw, size_t mws,
                                                           const double *__restrict__ vol, int npx, int npy, int n_patches,
@@ -136,7 +139,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_data_gram(int nx, int ny, int nz
 {
     constexpr int R = GramRows<T>::R, PS = GramRows<T>::PS, RB = R / 8;
     extern __shared__ double2 gr_smem[];
-    T *const stage = reinterpret_cast<T *>(gr_smem);                          // [GR_FIELDS][GR_EDGES]
+    S *const stage = reinterpret_cast<S *>(gr_smem);                          // [GR_FIELDS][GR_EDGES]
     double *const panel_a = reinterpret_cast<double *>(stage + GR_FIELDS * GR_EDGES);   // [GR_CELLS][PS]
     double *const panel_b = panel_a + GR_CELLS * PS;
     const int ta = blockIdx.y / n_tiles_b, tb = blockIdx.y % n_tiles_b;
@@ -163,8 +166,8 @@ __global__ __launch_bounds__(GR_THREADS) void k_data_gram(int nx, int ny, int nz
         for (int p = 0; p < 3; ++p) {
             if (row_x != p && row_y != p && row_z != p) continue;
             const double f = inside ? sqrt(mw[p * mws + c]) * q4 : 0.0;
-            gram_panel<T>(nx, ny, nz, A, ta, x0, y0, z0, p, row_x, row_y, row_z, f, stage, panel_a);
-            if (!one_panel) gram_panel<T>(nx, ny, nz, B, tb, x0, y0, z0, p, row_x, row_y, row_z, f, stage, panel_b);
+            gram_panel<T, S>(nx, ny, nz, A, ta, x0, y0, z0, p, row_x, row_y, row_z, f, stage, panel_a);
+            if (!one_panel) gram_panel<T, S>(nx, ny, nz, B, tb, x0, y0, z0, p, row_x, row_y, row_z, f, stage, panel_b);
             __syncthreads();
             const double *pa = panel_a + (wave * (GR_CELLS / GR_WAVES)) * PS + li * RB;
             const double *pb = (one_panel ? panel_a : panel_b) + (wave * (GR_CELLS / GR_WAVES)) * PS + lj * RB;
@@ -244,15 +247,15 @@ template <class T> T gram_scale(double re, double im);
 template <> inline double gram_scale<double>(double re, double) { return re; }
 template <> inline cplx gram_scale<cplx>(double re, double im) { return cplx(re, im); }
 
-template <class T>
-int launch_data_gram(int nx, int ny, int nz, const GramSide<T> &A, const GramSide<T> &B, int n_tiles_a, int n_tiles_b, int same,
+template <class T, class S>
+int launch_data_gram(int nx, int ny, int nz, const GramSide<T, S> &A, const GramSide<T, S> &B, int n_tiles_a, int n_tiles_b, int same,
                      int n_wg, int row_x, int row_y, int row_z, const double *mw, size_t mws, const double *vol, double *out,
                      size_t ld, double *ws, hipStream_t st)
 {
-    constexpr size_t smem = gram_lds_bytes<T>();
+    constexpr size_t smem = gram_lds_bytes<T, S>();
     constexpr int c = (int)(sizeof(T) / sizeof(double));
-    if (smem > (size_t)64 * 1024) HIP_TRY(allow_lds((const void *)&k_data_gram<T>, smem));
-    hipLaunchKernelGGL(k_data_gram<T>, dim3(n_wg, n_tiles_a * n_tiles_b), dim3(GR_THREADS), smem, st, nx, ny, nz, A, B, n_tiles_b,
+    if (smem > (size_t)64 * 1024) HIP_TRY(allow_lds((const void *)&k_data_gram<T, S>, smem));
+    hipLaunchKernelGGL((k_data_gram<T, S>), dim3(n_wg, n_tiles_a * n_tiles_b), dim3(GR_THREADS), smem, st, nx, ny, nz, A, B, n_tiles_b,
                        same, row_x, row_y, row_z, mw, mws, vol, cdiv(nx, GR_PX), cdiv(ny, GR_PY), (int)gram_patches(nx, ny, nz), ws);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_data_gram_reduce, dim3(cdiv(c * B.ns * B.nr, 16), cdiv(c * A.ns * A.nr, 16)), dim3(256), 0, st, c, A.ns,
@@ -261,35 +264,27 @@ int launch_data_gram(int nx, int ny, int nz, const GramSide<T> &A, const GramSid
     return 0;
 }
 
-template <class T>
+template <class T, class S>
 int data_gram(int nx, int ny, int nz, const void *e_a, size_t es_a, int ns_a, const void *x_a, size_t xs_a, int nr_a,
               double sa_re, double sa_im, const void *e_b, size_t es_b, int ns_b, const void *x_b, size_t xs_b, int nr_b,
               double sb_re, double sb_im, int n_wg, int row_x, int row_y, int row_z, const double *mw, size_t mws,
               const double *vol, double *out, size_t ld, double *ws, hipStream_t st)
 {
-    const GramSide<T> A{(const T *)e_a, es_a, ns_a, (const T *)x_a, xs_a, nr_a, gram_scale<T>(sa_re, sa_im), cdiv(nr_a, GR_TR)};
-    const GramSide<T> B{(const T *)e_b, es_b, ns_b, (const T *)x_b, xs_b, nr_b, gram_scale<T>(sb_re, sb_im), cdiv(nr_b, GR_TR)};
+    const GramSide<T, S> A{(const S *)e_a, es_a, ns_a, (const S *)x_a, xs_a, nr_a, gram_scale<T>(sa_re, sa_im), cdiv(nr_a, GR_TR)};
+    const GramSide<T, S> B{(const S *)e_b, es_b, ns_b, (const S *)x_b, xs_b, nr_b, gram_scale<T>(sb_re, sb_im), cdiv(nr_b, GR_TR)};
     const int same = e_a == e_b && x_a == x_b && es_a == es_b && xs_a == xs_b && ns_a == ns_b && nr_a == nr_b &&
                      sa_re == sb_re && (sizeof(T) == sizeof(double) || sa_im == sb_im);
-    return launch_data_gram<T>(nx, ny, nz, A, B, cdiv(ns_a, GR_TS) * A.ntr, cdiv(ns_b, GR_TS) * B.ntr, same, n_wg, row_x, row_y,
+    return launch_data_gram<T, S>(nx, ny, nz, A, B, cdiv(ns_a, GR_TS) * A.ntr, cdiv(ns_b, GR_TS) * B.ntr, same, n_wg, row_x, row_y,
                                row_z, mw, mws, vol, out, ld, ws, st);
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t emg3d_data_gram_ws_len(int nx, int ny, int nz, int is_complex, int n_a, int n_b)
-{
-    if (nx < 1 || ny < 1 || nz < 1 || n_a < 1 || n_b < 1) return 0;
-    return gram_ws_len(nx, ny, nz, is_complex, n_a, n_b);
-}
-
-int emg3d_dev_data_gram(int nx, int ny, int nz, int is_complex, const void *e_a, size_t e_a_stride, int ns_a, const void *x_a,
-                        size_t x_a_stride, int nr_a, double scale_a_re, double scale_a_im, const void *e_b, size_t e_b_stride,
-                        int ns_b, const void *x_b, size_t x_b_stride, int nr_b, double scale_b_re, double scale_b_im, int row_x,
-                        int row_y, int row_z, const double *model_weights, size_t mw_stride, const double *volumes, double *out,
-                        size_t ld, double *ws, size_t ws_len, void *stream)
+// The checks of emg3d_dev_data_gram and of its _sp sibling (SP: the stacks of BOTH sides in single precision).
+template <bool SP>
+int data_gram_checked(int nx, int ny, int nz, int is_complex, const void *e_a, size_t e_a_stride, int ns_a, const void *x_a,
+                      size_t x_a_stride, int nr_a, double scale_a_re, double scale_a_im, const void *e_b, size_t e_b_stride,
+                      int ns_b, const void *x_b, size_t x_b_stride, int nr_b, double scale_b_re, double scale_b_im, int row_x,
+                      int row_y, int row_z, const double *model_weights, size_t mw_stride, const double *volumes, double *out,
+                      size_t ld, double *ws, size_t ws_len, void *stream)
 {
     if (!e_a || !x_a || !e_b || !x_b || !model_weights || !volumes || !out || !ws)
         return fail(EMG3D_ERR_BADARG, "data_gram: null pointer");
@@ -311,12 +306,46 @@ int emg3d_dev_data_gram(int nx, int ny, int nz, int is_complex, const void *e_a,
     // workgroups per pair of tiles: what the workspace of THESE sizes holds -- not what the caller passed
     const size_t R = (size_t)GR_DATA * c;
     const int n_wg = (int)std::min(std::min(gram_patches(nx, ny, nz), (size_t)GR_MAX_WG), need / (R * R * tiles));
-    return is_complex ? data_gram<cplx>(nx, ny, nz, e_a, e_a_stride, ns_a, x_a, x_a_stride, nr_a, scale_a_re, scale_a_im, e_b,
-                                        e_b_stride, ns_b, x_b, x_b_stride, nr_b, scale_b_re, scale_b_im, n_wg, row_x, row_y,
-                                        row_z, model_weights, mw_stride, volumes, out, ld, ws, (hipStream_t)stream)
-                      : data_gram<double>(nx, ny, nz, e_a, e_a_stride, ns_a, x_a, x_a_stride, nr_a, scale_a_re, scale_a_im, e_b,
-                                          e_b_stride, ns_b, x_b, x_b_stride, nr_b, scale_b_re, scale_b_im, n_wg, row_x, row_y,
-                                          row_z, model_weights, mw_stride, volumes, out, ld, ws, (hipStream_t)stream);
+    using SC = std::conditional_t<SP, emg::cplxf, cplx>;
+    using SR = std::conditional_t<SP, float, double>;
+    return is_complex ? data_gram<cplx, SC>(nx, ny, nz, e_a, e_a_stride, ns_a, x_a, x_a_stride, nr_a, scale_a_re, scale_a_im, e_b,
+                                            e_b_stride, ns_b, x_b, x_b_stride, nr_b, scale_b_re, scale_b_im, n_wg, row_x, row_y,
+                                            row_z, model_weights, mw_stride, volumes, out, ld, ws, (hipStream_t)stream)
+                      : data_gram<double, SR>(nx, ny, nz, e_a, e_a_stride, ns_a, x_a, x_a_stride, nr_a, scale_a_re, scale_a_im,
+                                              e_b, e_b_stride, ns_b, x_b, x_b_stride, nr_b, scale_b_re, scale_b_im, n_wg, row_x, row_y,
+                                              row_z, model_weights, mw_stride, volumes, out, ld, ws, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t emg3d_data_gram_ws_len(int nx, int ny, int nz, int is_complex, int n_a, int n_b)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || n_a < 1 || n_b < 1) return 0;
+    return gram_ws_len(nx, ny, nz, is_complex, n_a, n_b);
+}
+
+int emg3d_dev_data_gram(int nx, int ny, int nz, int is_complex, const void *e_a, size_t e_a_stride, int ns_a, const void *x_a,
+                        size_t x_a_stride, int nr_a, double scale_a_re, double scale_a_im, const void *e_b, size_t e_b_stride,
+                        int ns_b, const void *x_b, size_t x_b_stride, int nr_b, double scale_b_re, double scale_b_im, int row_x,
+                        int row_y, int row_z, const double *model_weights, size_t mw_stride, const double *volumes, double *out,
+                        size_t ld, double *ws, size_t ws_len, void *stream)
+{
+    return data_gram_checked<false>(nx, ny, nz, is_complex, e_a, e_a_stride, ns_a, x_a, x_a_stride, nr_a, scale_a_re,
+                                    scale_a_im, e_b, e_b_stride, ns_b, x_b, x_b_stride, nr_b, scale_b_re, scale_b_im, row_x, row_y,
+                                    row_z, model_weights, mw_stride, volumes, out, ld, ws, ws_len, stream);
+}
+
+int emg3d_dev_data_gram_sp(int nx, int ny, int nz, int is_complex, const void *e_a, size_t e_a_stride, int ns_a, const void *x_a,
+                           size_t x_a_stride, int nr_a, double scale_a_re, double scale_a_im, const void *e_b, size_t e_b_stride,
+                           int ns_b, const void *x_b, size_t x_b_stride, int nr_b, double scale_b_re, double scale_b_im, int row_x,
+                           int row_y, int row_z, const double *model_weights, size_t mw_stride, const double *volumes, double *out,
+                           size_t ld, double *ws, size_t ws_len, void *stream)
+{
+    return data_gram_checked<true>(nx, ny, nz, is_complex, e_a, e_a_stride, ns_a, x_a, x_a_stride, nr_a, scale_a_re,
+                                   scale_a_im, e_b, e_b_stride, ns_b, x_b, x_b_stride, nr_b, scale_b_re, scale_b_im, row_x, row_y,
+                                   row_z, model_weights, mw_stride, volumes, out, ld, ws, ws_len, stream);
 }
 
 }  // extern "C"

@@ -24,17 +24,20 @@ constexpr int HD_EDGES = HD_PX * (HD_PY + 1) * (HD_PZ + 1); // x-edges of a patc
 static_assert((HD_PX + 1) * HD_PY * (HD_PZ + 1) <= HD_EDGES && (HD_PX + 1) * (HD_PY + 1) * HD_PZ <= HD_EDGES, "LDS tile");
 static_assert(HD_THREADS == 256 && HD_THREADS % HD_PX == 0, "one cell per thread, rows of HD_PX threads");
 
-template <class T> constexpr size_t hessian_lds_bytes() { return (size_t)(HD_TS + HD_TR) * HD_EDGES * sizeof(T); }
+// S: the type the stacks are stored in (T, or its single-precision partner). The edges are staged in LDS AS STORED and
+// widened when a thread reads them for its pair sums: the narrow instantiations ask for half the LDS; every operation
+// is T's.
+template <class S> constexpr size_t hessian_lds_bytes() { return (size_t)(HD_TS + HD_TR) * HD_EDGES * sizeof(S); }
 
-template <class T>
-__global__ __launch_bounds__(HD_THREADS) void k_hessian_diagonal(int nx, int ny, int nz, const T *__restrict__ e, size_t es,
-                                                                 int ns, const T *__restrict__ x, size_t xs, int nr,
+template <class T, class S>
+__global__ __launch_bounds__(HD_THREADS) void k_hessian_diagonal(int nx, int ny, int nz, const S *__restrict__ e, size_t es,
+                                                                 int ns, const S *__restrict__ x, size_t xs, int nr,
                                                                  const double *__restrict__ wt, int row_x, int row_y,
                                                                  int row_z, double scale, const double *__restrict__ vol,
                                                                  double *__restrict__ h, size_t hs)
 {
     extern __shared__ double2 hd_smem[];
-    T *const lds = reinterpret_cast<T *>(hd_smem);          // [HD_TS + HD_TR][HD_EDGES]
+    S *const lds = reinterpret_cast<S *>(hd_smem);          // [HD_TS + HD_TR][HD_EDGES]
     const int t = threadIdx.x;
     const int tx = t % HD_PX, trow = t / HD_PX;             // staging: thread tx of row trow
     const int ty = trow % HD_PY, tz = trow / HD_PY;         // the thread's cell in the patch
@@ -66,27 +69,29 @@ __global__ __launch_bounds__(HD_THREADS) void k_hessian_diagonal(int nx, int ny,
                             const int gi = x0 + li;
                             const bool in = gi < gnx && gj < gny && gk < gnz;
                             const size_t g = goff + gi + (size_t)gnx * (gj + (size_t)gny * gk);
-                            T *const dst = lds + (li + lx * row);
+                            S *const dst = lds + (li + lx * row);
 #pragma unroll
                             for (int i = 0; i < HD_TS; ++i)
-                                dst[i * HD_EDGES] = in && s0 + i < ns ? e[(size_t)(s0 + i) * es + g] : emg::zero<T>();
+                                dst[i * HD_EDGES] =
+                                    in && s0 + i < ns ? e[(size_t)(s0 + i) * es + g] : emg::narrow<S>(emg::zero<T>());
 #pragma unroll
                             for (int j = 0; j < HD_TR; ++j)
-                                dst[(HD_TS + j) * HD_EDGES] = in && r0 + j < nr ? x[(size_t)(r0 + j) * xs + g] : emg::zero<T>();
+                                dst[(HD_TS + j) * HD_EDGES] =
+                                    in && r0 + j < nr ? x[(size_t)(r0 + j) * xs + g] : emg::narrow<S>(emg::zero<T>());
                         }
                     }
                     __syncthreads();
                     // the four d-edges of the cell in the order of edges_to_cell: x: y inner, z outer; y: x, z; z: x, y
                     const int o1 = d == 0 ? lx : 1, o2 = d == 2 ? lx : lx * ly;
-                    const T *const src = lds + (tx + lx * (ty + ly * tz));
+                    const S *const src = lds + (tx + lx * (ty + ly * tz));
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const T *const q = src + ((k & 1) * o1 + (k >> 1) * o2);
+                        const S *const q = src + ((k & 1) * o1 + (k >> 1) * o2);
                         T ev[HD_TS], xv[HD_TR];
 #pragma unroll
-                        for (int i = 0; i < HD_TS; ++i) ev[i] = q[i * HD_EDGES];
+                        for (int i = 0; i < HD_TS; ++i) ev[i] = emg::widen(q[i * HD_EDGES]);
 #pragma unroll
-                        for (int j = 0; j < HD_TR; ++j) xv[j] = q[(HD_TS + j) * HD_EDGES];
+                        for (int j = 0; j < HD_TR; ++j) xv[j] = emg::widen(q[(HD_TS + j) * HD_EDGES]);
 #pragma unroll
                         for (int i = 0; i < HD_TS; ++i)
 #pragma unroll
@@ -118,27 +123,25 @@ __global__ __launch_bounds__(HD_THREADS) void k_hessian_diagonal(int nx, int ny,
     if (row_x == 2 || row_y == 2 || row_z == 2) h[2 * hs + c] += f * h2;
 }
 
-template <class T>
+template <class T, class S>
 int launch_hessian_diagonal(int nx, int ny, int nz, const void *e, size_t es, int ns, const void *x, size_t xs, int nr,
                             const double *wt, int row_x, int row_y, int row_z, double scale, const double *vol, double *h,
                             size_t hs, hipStream_t st)
 {
-    constexpr size_t smem = hessian_lds_bytes<T>();
-    if (smem > (size_t)64 * 1024) HIP_TRY(allow_lds((const void *)&k_hessian_diagonal<T>, smem));
+    constexpr size_t smem = hessian_lds_bytes<S>();
+    if (smem > (size_t)64 * 1024) HIP_TRY(allow_lds((const void *)&k_hessian_diagonal<T, S>, smem));
     const dim3 grid(cdiv(nx, HD_PX), cdiv(ny, HD_PY), cdiv(nz, HD_PZ));
-    hipLaunchKernelGGL(k_hessian_diagonal<T>, grid, dim3(HD_THREADS), smem, st, nx, ny, nz, (const T *)e, es, ns, (const T *)x,
-                       xs, nr, wt, row_x, row_y, row_z, scale, vol, h, hs);
+    hipLaunchKernelGGL((k_hessian_diagonal<T, S>), grid, dim3(HD_THREADS), smem, st, nx, ny, nz, (const S *)e, es, ns,
+                       (const S *)x, xs, nr, wt, row_x, row_y, row_z, scale, vol, h, hs);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int emg3d_dev_hessian_diagonal(int nx, int ny, int nz, int is_complex, const void *e, size_t e_stride, int ns, const void *x,
-                               size_t x_stride, int nr, const double *weights, int row_x, int row_y, int row_z, double scale,
-                               const double *volumes, double *h, size_t h_stride, void *stream)
+// The checks of emg3d_dev_hessian_diagonal and of its _sp sibling (SP: stacks in single precision).
+template <bool SP>
+int hessian_diagonal(int nx, int ny, int nz, int is_complex, const void *e, size_t e_stride, int ns, const void *x,
+                     size_t x_stride, int nr, const double *weights, int row_x, int row_y, int row_z, double scale,
+                     const double *volumes, double *h, size_t h_stride, void *stream)
 {
     if (nx < 1 || ny < 1 || nz < 1 || ns < 1 || nr < 1 || !e || !x || !weights || !volumes || !h)
         return fail(EMG3D_ERR_BADARG, "hessian_diagonal: bad argument");
@@ -150,10 +153,32 @@ int emg3d_dev_hessian_diagonal(int nx, int ny, int nz, int is_complex, const voi
         return fail(EMG3D_ERR_BADARG, "hessian_diagonal: a stride is smaller than its row");
     if (cdiv(ny, HD_PY) > 65535 || cdiv(nz, HD_PZ) > 65535)
         return fail(EMG3D_ERR_BADARG, "hessian_diagonal: too large for one launch");
-    return is_complex ? launch_hessian_diagonal<cplx>(nx, ny, nz, e, e_stride, ns, x, x_stride, nr, weights, row_x, row_y,
-                                                      row_z, scale, volumes, h, h_stride, (hipStream_t)stream)
-                      : launch_hessian_diagonal<double>(nx, ny, nz, e, e_stride, ns, x, x_stride, nr, weights, row_x, row_y,
-                                                        row_z, scale, volumes, h, h_stride, (hipStream_t)stream);
+    using C = std::conditional_t<SP, emg::cplxf, cplx>;
+    using R = std::conditional_t<SP, float, double>;
+    return is_complex ? launch_hessian_diagonal<cplx, C>(nx, ny, nz, e, e_stride, ns, x, x_stride, nr, weights, row_x, row_y,
+                                                         row_z, scale, volumes, h, h_stride, (hipStream_t)stream)
+                      : launch_hessian_diagonal<double, R>(nx, ny, nz, e, e_stride, ns, x, x_stride, nr, weights, row_x, row_y,
+                                                           row_z, scale, volumes, h, h_stride, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int emg3d_dev_hessian_diagonal(int nx, int ny, int nz, int is_complex, const void *e, size_t e_stride, int ns, const void *x,
+                               size_t x_stride, int nr, const double *weights, int row_x, int row_y, int row_z, double scale,
+                               const double *volumes, double *h, size_t h_stride, void *stream)
+{
+    return hessian_diagonal<false>(nx, ny, nz, is_complex, e, e_stride, ns, x, x_stride, nr, weights, row_x, row_y, row_z, scale,
+                                   volumes, h, h_stride, stream);
+}
+
+int emg3d_dev_hessian_diagonal_sp(int nx, int ny, int nz, int is_complex, const void *e, size_t e_stride, int ns, const void *x,
+                                  size_t x_stride, int nr, const double *weights, int row_x, int row_y, int row_z, double scale,
+                                  const double *volumes, double *h, size_t h_stride, void *stream)
+{
+    return hessian_diagonal<true>(nx, ny, nz, is_complex, e, e_stride, ns, x, x_stride, nr, weights, row_x, row_y, row_z, scale,
+                                  volumes, h, h_stride, stream);
 }
 
 }  // extern "C"

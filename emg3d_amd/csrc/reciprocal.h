@@ -5,6 +5,8 @@
 // are reductions over the kept fields: no solve. Four kernels, plain fp64, no atomics, every sum in a fixed
 // order that depends on the sizes only. Fields of one kind are stacked: field i starts i * stride elements
 // behind field 0 (stride >= n; what lies between n and stride is never read).
+// The two reductions over the stacks, dots and combine, separate the type S the stacks are STORED in from the type T
+// of the arithmetic: S = T, or T's single-precision partner of cplx.h, widened as it is loaded.
 // Included at the end of kernels.hip (one translation unit), after adjoint.h, whose gathers it shares.
 #pragma once
 
@@ -62,13 +64,42 @@ __device__ __forceinline__ cplx shfl_down_t(cplx a, int off)
     return cplx(__shfl_down(a.re, off, 64), __shfl_down(a.im, off, 64));
 }
 
-template <class T>
-__global__ __launch_bounds__(DOT_THREADS) void k_sensitivity_dots(size_t n, const T *e, size_t es, int ns, const T *x,
+// One k of the tile: acc[i][j] += (w[k] e_i[k]) x_j[k], the fields widened as they arrive.
+template <class T, class S>
+__device__ __forceinline__ void dots_step(size_t k, const double *w, const S *const *ep, const S *const *xp,
+                                          T (&acc)[DOT_TS][DOT_TR])
+{
+    const double wk = w[k];
+    T xv[DOT_TR];
+#pragma unroll
+    for (int j = 0; j < DOT_TR; ++j) xv[j] = emg::widen(xp[j][k]);
+#pragma unroll
+    for (int i = 0; i < DOT_TS; ++i) {
+        const T we = wk * emg::widen(ep[i][k]);
+#pragma unroll
+        for (int j = 0; j < DOT_TR; ++j) acc[i][j] = emg::mad(we, xv[j], acc[i][j]);
+    }
+}
+
+// V consecutive values of a stack, fetched with 16-byte loads: the address must be a multiple of 16.
+template <class S, int V> struct alignas(16) Pack { S v[V]; };
+template <class S, int V> __device__ __forceinline__ Pack<S, V> load_pack(const S *p)
+{
+    return *reinterpret_cast<const Pack<S, V> *>(p);
+}
+
+// S: the type the stacks are stored in (T, or its single-precision partner: values are widened when they are loaded,
+// every operation is T's). V: consecutive k per lane. V = 1: element-wise loads -- 16 bytes each for S = cplx. V > 1
+// (S narrower than T only): a lane takes V consecutive k with ONE 16-byte load per field (V = 2 for cplxf, 4 for
+// float), which needs every row of both stacks and w on a 16-byte boundary: launch_dots decides. The last lane of a
+// row that is no multiple of V long goes element by element, so nothing behind n is read.
+template <class T, class S, int V>
+__global__ __launch_bounds__(DOT_THREADS) void k_sensitivity_dots(size_t n, const S *e, size_t es, int ns, const S *x,
                                                                   size_t xs, int nr, const double *w, size_t nchunk,
                                                                   T *partial)
 {
     const int s0 = blockIdx.y * DOT_TS, r0 = blockIdx.z * DOT_TR;
-    const T *ep[DOT_TS], *xp[DOT_TR];
+    const S *ep[DOT_TS], *xp[DOT_TR];
 #pragma unroll
     for (int i = 0; i < DOT_TS; ++i) ep[i] = e + (size_t)min(s0 + i, ns - 1) * es;
 #pragma unroll
@@ -80,20 +111,37 @@ __global__ __launch_bounds__(DOT_THREADS) void k_sensitivity_dots(size_t n, cons
         for (int j = 0; j < DOT_TR; ++j) acc[i][j] = emg::zero<T>();
     const size_t k0 = (size_t)blockIdx.x * DOT_CHUNK;
     const size_t k1 = k0 + DOT_CHUNK < n ? k0 + DOT_CHUNK : n;
-    for (size_t kb = k0 + threadIdx.x; kb < k1; kb += (size_t)DOT_THREADS * DOT_UNROLL) {
+    if constexpr (V == 1) {
+        for (size_t kb = k0 + threadIdx.x; kb < k1; kb += (size_t)DOT_THREADS * DOT_UNROLL) {
 #pragma unroll
-        for (int u = 0; u < DOT_UNROLL; ++u) {
-            const size_t k = kb + (size_t)u * DOT_THREADS;
-            if (k < k1) {
-                const double wk = w[k];
-                T xv[DOT_TR];
+            for (int u = 0; u < DOT_UNROLL; ++u) {
+                const size_t k = kb + (size_t)u * DOT_THREADS;
+                if (k < k1) dots_step<T, S>(k, w, ep, xp, acc);
+            }
+        }
+    } else {
+        static_assert(DOT_CHUNK % V == 0 && sizeof(S) * V == 16, "a chunk starts on a 16-byte boundary of every row");
+        for (size_t kb = k0 + (size_t)threadIdx.x * V; kb < k1; kb += (size_t)DOT_THREADS * DOT_UNROLL * V) {
 #pragma unroll
-                for (int j = 0; j < DOT_TR; ++j) xv[j] = xp[j][k];
+            for (int u = 0; u < DOT_UNROLL; ++u) {
+                const size_t k = kb + (size_t)u * DOT_THREADS * V;
+                if (k + V <= k1) {
+                    const Pack<double, V> wk = load_pack<double, V>(w + k);
+                    Pack<S, V> xv[DOT_TR];
 #pragma unroll
-                for (int i = 0; i < DOT_TS; ++i) {
-                    const T we = wk * ep[i][k];
+                    for (int j = 0; j < DOT_TR; ++j) xv[j] = load_pack<S, V>(xp[j] + k);
 #pragma unroll
-                    for (int j = 0; j < DOT_TR; ++j) acc[i][j] = emg::mad(we, xv[j], acc[i][j]);
+                    for (int i = 0; i < DOT_TS; ++i) {
+                        const Pack<S, V> ev = load_pack<S, V>(ep[i] + k);
+#pragma unroll
+                        for (int m = 0; m < V; ++m) {
+                            const T we = wk.v[m] * emg::widen(ev.v[m]);
+#pragma unroll
+                            for (int j = 0; j < DOT_TR; ++j) acc[i][j] = emg::mad(we, emg::widen(xv[j].v[m]), acc[i][j]);
+                        }
+                    }
+                } else {
+                    for (size_t kk = k; kk < k1; ++kk) dots_step<T, S>(kk, w, ep, xp, acc);
                 }
             }
         }
@@ -139,16 +187,13 @@ __global__ __launch_bounds__(256) void k_sensitivity_dots_final(const T *partial
 // the compiler fetches them with scalar loads.
 constexpr int CMB_XR = 8;
 
-template <class T>
-__global__ __launch_bounds__(256) void k_sensitivity_combine(size_t n, const T *__restrict__ e, size_t es, int ns,
-                                                             const T *__restrict__ x, size_t xs, int nr,
-                                                             const T *__restrict__ coef, T *__restrict__ t)
+template <class T, class S>
+__device__ __forceinline__ T combine_one(size_t k, const S *__restrict__ e, size_t es, int ns, const S *__restrict__ x,
+                                         size_t xs, int nr, const T *__restrict__ coef)
 {
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
     T xv[CMB_XR];
 #pragma unroll
-    for (int j = 0; j < CMB_XR; ++j) xv[j] = x[(size_t)min(j, nr - 1) * xs + k];
+    for (int j = 0; j < CMB_XR; ++j) xv[j] = emg::widen(x[(size_t)min(j, nr - 1) * xs + k]);
     T sum = emg::zero<T>();
     for (int s = 0; s < ns; ++s) {
         const T *c = coef + (size_t)s * nr;
@@ -156,27 +201,146 @@ __global__ __launch_bounds__(256) void k_sensitivity_combine(size_t n, const T *
 #pragma unroll
         for (int j = 0; j < CMB_XR; ++j)
             if (j < nr) u = emg::mad(c[j], xv[j], u);
-        for (int r = CMB_XR; r < nr; ++r) u = emg::mad(c[r], x[(size_t)r * xs + k], u);
-        sum = emg::mad(e[(size_t)s * es + k], u, sum);
+        for (int r = CMB_XR; r < nr; ++r) u = emg::mad(c[r], emg::widen(x[(size_t)r * xs + k]), u);
+        sum = emg::mad(emg::widen(e[(size_t)s * es + k]), u, sum);
     }
-    t[k] = sum;
+    return sum;
+}
+
+// S, V: as in k_sensitivity_dots. V > 1: one thread per V consecutive k, a 16-byte load per field and 16-byte stores of
+// t (every row of both stacks and t on a 16-byte boundary: the launcher decides); each of the V sums is combine_one's,
+// term by term, so t does not depend on V. The last thread of an n that is no multiple of V goes element by element.
+template <class T, class S, int V>
+__global__ __launch_bounds__(256) void k_sensitivity_combine(size_t n, const S *__restrict__ e, size_t es, int ns,
+                                                             const S *__restrict__ x, size_t xs, int nr,
+                                                             const T *__restrict__ coef, T *__restrict__ t)
+{
+    const size_t k = ((size_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (k >= n) return;
+    if constexpr (V == 1) {
+        t[k] = combine_one<T, S>(k, e, es, ns, x, xs, nr, coef);
+    } else {
+        static_assert(sizeof(S) * V == 16, "one 16-byte load per field");
+        if (k + V > n) {
+            for (size_t kk = k; kk < n; ++kk) t[kk] = combine_one<T, S>(kk, e, es, ns, x, xs, nr, coef);
+            return;
+        }
+        Pack<S, V> xv[CMB_XR];
+#pragma unroll
+        for (int j = 0; j < CMB_XR; ++j) xv[j] = load_pack<S, V>(x + (size_t)min(j, nr - 1) * xs + k);
+        Pack<T, V> sum;
+#pragma unroll
+        for (int m = 0; m < V; ++m) sum.v[m] = emg::zero<T>();
+        for (int s = 0; s < ns; ++s) {
+            const T *c = coef + (size_t)s * nr;
+            T u[V];
+#pragma unroll
+            for (int m = 0; m < V; ++m) u[m] = emg::zero<T>();
+#pragma unroll
+            for (int j = 0; j < CMB_XR; ++j)
+                if (j < nr) {
+#pragma unroll
+                    for (int m = 0; m < V; ++m) u[m] = emg::mad(c[j], emg::widen(xv[j].v[m]), u[m]);
+                }
+            for (int r = CMB_XR; r < nr; ++r) {
+                const Pack<S, V> xr = load_pack<S, V>(x + (size_t)r * xs + k);
+#pragma unroll
+                for (int m = 0; m < V; ++m) u[m] = emg::mad(c[r], emg::widen(xr.v[m]), u[m]);
+            }
+            const Pack<S, V> ev = load_pack<S, V>(e + (size_t)s * es + k);
+#pragma unroll
+            for (int m = 0; m < V; ++m) sum.v[m] = emg::mad(emg::widen(ev.v[m]), u[m], sum.v[m]);
+        }
+        *reinterpret_cast<Pack<T, V> *>(t + k) = sum;
+    }
 }
 
 inline size_t dots_chunks(size_t n) { return (n + DOT_CHUNK - 1) / DOT_CHUNK; }
 
-template <class T>
-int launch_dots(size_t n, const void *e, size_t es, int ns, const void *x, size_t xs, int nr, const double *w, T scale,
-                void *out, double *ws, hipStream_t st)
+// Every row of a stack of S starts on a 16-byte boundary: the base does, and the stride is a whole number of them.
+template <class S> inline bool rows_on_16_bytes(const void *base, size_t stride)
+{
+    return (uintptr_t)base % 16 == 0 && stride * sizeof(S) % 16 == 0;
+}
+
+template <class T, class S, int V>
+int launch_dots_as(size_t n, const void *e, size_t es, int ns, const void *x, size_t xs, int nr, const double *w, T scale,
+                   void *out, double *ws, hipStream_t st)
 {
     const size_t nchunk = dots_chunks(n);
     const dim3 grid((unsigned)nchunk, cdiv(ns, DOT_TS), cdiv(nr, DOT_TR));
-    hipLaunchKernelGGL(k_sensitivity_dots<T>, grid, dim3(DOT_THREADS), 0, st, n, (const T *)e, es, ns, (const T *)x, xs, nr, w,
-                       nchunk, (T *)ws);
+    hipLaunchKernelGGL((k_sensitivity_dots<T, S, V>), grid, dim3(DOT_THREADS), 0, st, n, (const S *)e, es, ns, (const S *)x, xs,
+                       nr, w, nchunk, (T *)ws);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_sensitivity_dots_final<T>, dim3((unsigned)(ns * nr)), dim3(256), 0, st, (const T *)ws, nchunk, scale,
                        (T *)out);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// Stacks stored as S. Narrow stacks: 16-byte loads (V = 16 / sizeof(S) consecutive k per lane) where every row of
+// both stacks and w allow them, element-wise loads otherwise -- decided here, from the addresses and strides alone.
+template <class T, class S>
+int launch_dots(size_t n, const void *e, size_t es, int ns, const void *x, size_t xs, int nr, const double *w, T scale,
+                void *out, double *ws, hipStream_t st)
+{
+    if constexpr (sizeof(S) < sizeof(T)) {
+        if (rows_on_16_bytes<S>(e, es) && rows_on_16_bytes<S>(x, xs) && (uintptr_t)w % 16 == 0)
+            return launch_dots_as<T, S, (int)(16 / sizeof(S))>(n, e, es, ns, x, xs, nr, w, scale, out, ws, st);
+    }
+    return launch_dots_as<T, S, 1>(n, e, es, ns, x, xs, nr, w, scale, out, ws, st);
+}
+
+template <class T, class S>
+int launch_combine(size_t n, const void *e, size_t es, int ns, const void *x, size_t xs, int nr, const void *coef, void *t,
+                   hipStream_t st)
+{
+    if constexpr (sizeof(S) < sizeof(T)) {
+        if (rows_on_16_bytes<S>(e, es) && rows_on_16_bytes<S>(x, xs) && (uintptr_t)t % 16 == 0) {
+            constexpr int V = (int)(16 / sizeof(S));
+            const size_t nblk = ((n + V - 1) / V + 255) / 256;
+            hipLaunchKernelGGL((k_sensitivity_combine<T, S, V>), dim3((unsigned)nblk), dim3(256), 0, st, n, (const S *)e, es, ns,
+                               (const S *)x, xs, nr, (const T *)coef, (T *)t);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL((k_sensitivity_combine<T, S, 1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const S *)e, es,
+                       ns, (const S *)x, xs, nr, (const T *)coef, (T *)t);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The checks of emg3d_dev_sensitivity_dots / _combine and of their _sp siblings (SP: stacks in single precision).
+template <bool SP>
+int sensitivity_dots(size_t n, int is_complex, const void *e, size_t e_stride, int ns, const void *x, size_t x_stride, int nr,
+                     const double *w, double scale_re, double scale_im, void *out, double *ws, size_t ws_len, void *stream)
+{
+    if (n < 1 || ns < 1 || nr < 1 || !e || !x || !w || !out || !ws || e_stride < n || x_stride < n)
+        return fail(EMG3D_ERR_BADARG, "sensitivity_dots: bad argument");
+    if (dots_chunks(n) > 0x7fffffffu || (size_t)ns * (size_t)nr > 0x7fffffffu || cdiv(ns, DOT_TS) > 65535 ||
+        cdiv(nr, DOT_TR) > 65535)
+        return fail(EMG3D_ERR_BADARG, "sensitivity_dots: too large for one launch");
+    if (ws_len < 2 * (size_t)ns * (size_t)nr * dots_chunks(n))
+        return fail(EMG3D_ERR_BADARG, "sensitivity_dots: workspace too small (emg3d_sensitivity_dots_ws_len)");
+    using C = std::conditional_t<SP, emg::cplxf, cplx>;
+    using R = std::conditional_t<SP, float, double>;
+    return is_complex ? launch_dots<cplx, C>(n, e, e_stride, ns, x, x_stride, nr, w, cplx(scale_re, scale_im), out, ws,
+                                             (hipStream_t)stream)
+                      : launch_dots<double, R>(n, e, e_stride, ns, x, x_stride, nr, w, scale_re, out, ws, (hipStream_t)stream);
+}
+
+template <bool SP>
+int sensitivity_combine(size_t n, int is_complex, const void *e, size_t e_stride, int ns, const void *x, size_t x_stride,
+                        int nr, const void *coef, void *t, void *stream)
+{
+    if (n < 1 || ns < 1 || nr < 1 || !e || !x || !coef || !t || e_stride < n || x_stride < n)
+        return fail(EMG3D_ERR_BADARG, "sensitivity_combine: bad argument");
+    if ((n + 255) / 256 > 0x7fffffffu) return fail(EMG3D_ERR_BADARG, "sensitivity_combine: too large for one launch");
+    using C = std::conditional_t<SP, emg::cplxf, cplx>;
+    using R = std::conditional_t<SP, float, double>;
+    return is_complex ? launch_combine<cplx, C>(n, e, e_stride, ns, x, x_stride, nr, coef, t, (hipStream_t)stream)
+                      : launch_combine<double, R>(n, e, e_stride, ns, x, x_stride, nr, coef, t, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -204,34 +368,28 @@ int emg3d_dev_sensitivity_dots(size_t n, int is_complex, const void *e, size_t e
                                size_t x_stride, int nr, const double *w, double scale_re, double scale_im, void *out,
                                double *ws, size_t ws_len, void *stream)
 {
-    if (n < 1 || ns < 1 || nr < 1 || !e || !x || !w || !out || !ws || e_stride < n || x_stride < n)
-        return fail(EMG3D_ERR_BADARG, "sensitivity_dots: bad argument");
-    if (dots_chunks(n) > 0x7fffffffu || (size_t)ns * (size_t)nr > 0x7fffffffu || cdiv(ns, DOT_TS) > 65535 ||
-        cdiv(nr, DOT_TR) > 65535)
-        return fail(EMG3D_ERR_BADARG, "sensitivity_dots: too large for one launch");
-    if (ws_len < emg3d_sensitivity_dots_ws_len(ns, nr, n))
-        return fail(EMG3D_ERR_BADARG, "sensitivity_dots: workspace too small (emg3d_sensitivity_dots_ws_len)");
-    return is_complex ? launch_dots<cplx>(n, e, e_stride, ns, x, x_stride, nr, w, cplx(scale_re, scale_im), out, ws,
-                                          (hipStream_t)stream)
-                      : launch_dots<double>(n, e, e_stride, ns, x, x_stride, nr, w, scale_re, out, ws, (hipStream_t)stream);
+    return sensitivity_dots<false>(n, is_complex, e, e_stride, ns, x, x_stride, nr, w, scale_re, scale_im, out, ws, ws_len,
+                                   stream);
+}
+
+int emg3d_dev_sensitivity_dots_sp(size_t n, int is_complex, const void *e, size_t e_stride, int ns, const void *x,
+                                  size_t x_stride, int nr, const double *w, double scale_re, double scale_im, void *out,
+                                  double *ws, size_t ws_len, void *stream)
+{
+    return sensitivity_dots<true>(n, is_complex, e, e_stride, ns, x, x_stride, nr, w, scale_re, scale_im, out, ws, ws_len,
+                                  stream);
 }
 
 int emg3d_dev_sensitivity_combine(size_t n, int is_complex, const void *e, size_t e_stride, int ns, const void *x,
                                   size_t x_stride, int nr, const void *coef, void *t, void *stream)
 {
-    if (n < 1 || ns < 1 || nr < 1 || !e || !x || !coef || !t || e_stride < n || x_stride < n)
-        return fail(EMG3D_ERR_BADARG, "sensitivity_combine: bad argument");
-    const size_t nblk = (n + 255) / 256;
-    if (nblk > 0x7fffffffu) return fail(EMG3D_ERR_BADARG, "sensitivity_combine: too large for one launch");
-    const dim3 grid((unsigned)nblk), block(256);
-    if (is_complex)
-        hipLaunchKernelGGL(k_sensitivity_combine<cplx>, grid, block, 0, (hipStream_t)stream, n, (const cplx *)e, e_stride, ns,
-                           (const cplx *)x, x_stride, nr, (const cplx *)coef, (cplx *)t);
-    else
-        hipLaunchKernelGGL(k_sensitivity_combine<double>, grid, block, 0, (hipStream_t)stream, n, (const double *)e, e_stride,
-                           ns, (const double *)x, x_stride, nr, (const double *)coef, (double *)t);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return sensitivity_combine<false>(n, is_complex, e, e_stride, ns, x, x_stride, nr, coef, t, stream);
+}
+
+int emg3d_dev_sensitivity_combine_sp(size_t n, int is_complex, const void *e, size_t e_stride, int ns, const void *x,
+                                     size_t x_stride, int nr, const void *coef, void *t, void *stream)
+{
+    return sensitivity_combine<true>(n, is_complex, e, e_stride, ns, x, x_stride, nr, coef, t, stream);
 }
 
 int emg3d_dev_edges_to_cells(int nx, int ny, int nz, int is_complex, const void *tx, const void *ty, const void *tz,

@@ -590,10 +590,25 @@ class ReciprocalSensitivity(Sensitivity):
     ``Re(J^H W J)`` in one pass (``emg3d_dev_hessian_diagonal``), and ``hessian_vec``, the product it
     preconditions; and ``data_gram``, the data-space normal matrix ``J^ diag(m) J^T`` of Occam and data-space
     Gauss-Newton schemes (``emg3d_dev_data_gram``, DESIGN.md 4.14: the rows of ``J^`` are generated in LDS and consumed
-    there, never written), with ``stack_data`` / ``unstack_data`` between data dictionaries and its real vectors."""
+    there, never written), with ``stack_data`` / ``unstack_data`` between data dictionaries and its real vectors.
+
+    field_dtype: ``'double'`` (default) keeps the fields as they are solved, ``n_edges x 16 B`` each. ``'single'``
+        keeps them as complex64 (Laplace domain: float32): half the bytes in HBM or pinned memory, over PCIe with
+        ``keep='host'``, and through the two HBM-bound products. Only the STORAGE is narrow: a solved
+        field is rounded once, when it is copied into its stack (its responses, ``synthetic``, are taken before that and
+        are the bits of ``'double'``), and widened when a kernel loads it; weights, coefficients, sums and results are
+        fp64 as before. Every kept value carries a relative error <= 2^-24, a product about 1e-7 of the sum of the
+        magnitudes of its terms -- two orders of magnitude below the default ``tol_gradient`` the receiver fields are
+        solved to. Rows of a stack are padded to a multiple of 16 B (``kept_bytes`` counts the padding). A value
+        beyond the range of float32 (3.4e38) would become inf: ``forward()`` raises ``FloatingPointError``; values
+        below its normal range (1.2e-38) lose digits or become 0, which is far below the rounding error of any product
+        relative to its largest terms -- there is no per-field scaling."""
 
     def __init__(self, model, sources, frequencies, receivers, solver_opts=None, tol_gradient=1e-5, costs=None,
-                 grids=None, interpolate_opts=None, magnetic=None, keep='device', batch=1):
+                 grids=None, interpolate_opts=None, magnetic=None, keep='device', batch=1, field_dtype='double'):
+        if not (isinstance(field_dtype, str) and field_dtype in ('double', 'single')):
+            raise ValueError(f"`field_dtype` must be 'double' or 'single'. Provided: {field_dtype!r}.")
+        self.field_dtype = field_dtype
         super().__init__(model, sources, frequencies, receivers, solver_opts=solver_opts, tol_gradient=tol_gradient,
                          costs=costs, grids=grids, interpolate_opts=interpolate_opts, magnetic=magnetic, keep=keep,
                          batch=batch)
@@ -627,26 +642,35 @@ class ReciprocalSensitivity(Sensitivity):
         ns, nr, nf = len(self.sources), len(self._rec[0]), len(self.frequencies)
         held = sum(len(t) for st in self._stacks.values() for t in st)
         return (f"ReciprocalSensitivity: {len(self.pairs)} pairs ({ns} sources x {nf} frequencies), {nr * nf} receiver "
-                f"fields ({nr} receivers x {nf} frequencies); keep={self.keep!r}, batch={self.batch}; kept fields: {held} "
+                f"fields ({nr} receivers x {nf} frequencies); keep={self.keep!r}, batch={self.batch}, "
+                f"field_dtype={self.field_dtype!r}; kept fields: {held} "
                 f"= {self.kept_bytes:,} B ({ {'device': 'HBM', 'host': 'pinned host memory'}[self.keep] })")
 
     @property
     def kept_bytes(self):
-        """Bytes held by the kept source and receiver fields ((n_sources + n_receivers) x n_edges x 16 B per
-        frequency, complex)."""
-        return int(sum(t.numel() * t.element_size() for st in self._stacks.values() for t in st))
+        """Bytes held by the kept source and receiver fields: (n_sources + n_receivers) x n_edges x 16 B per
+        frequency (complex) with ``field_dtype='double'``; ``'single'``: x 8 B, every row padded to a multiple of
+        16 B."""
+        return int(sum(t.untyped_storage().nbytes() for st in self._stacks.values() for t in st))
 
     # ----------------------------------------------------------------------------- set-up ---
     def _new_stack(self, rows, n, dtype, dev):
+        """A stack (rows, n) for solved fields of type ``dtype``. ``field_dtype='single'``: of the narrow partner type,
+        a view of a (rows, stride) allocation whose rows start on 16-byte boundaries (full-width loads in
+        ``emg3d_dev_sensitivity_dots_sp`` / ``_combine_sp``)."""
         import torch
+        if self.field_dtype == 'single':
+            dtype = {torch.complex128: torch.complex64, torch.float64: torch.float32}[dtype]
+        size = torch.empty(0, dtype=dtype).element_size()
+        stride = n if self.field_dtype == 'double' else -(-n * size // 16) * 16 // size
         if self.keep == 'host':
-            return torch.empty((rows, n), dtype=dtype, pin_memory=True)
-        need = rows * n * torch.empty(0, dtype=dtype).element_size()
+            return torch.empty((rows, stride), dtype=dtype, pin_memory=True)[:, :n]
+        need = rows * stride * size
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
         if need > free:
             raise MemoryError(f"ReciprocalSensitivity: a stack of {rows} kept fields needs {need:,} B of HBM, "
                               f"{free:,} B are free; keep='host' holds the fields in pinned host memory instead.")
-        return torch.empty((rows, n), dtype=dtype, device=dev)
+        return torch.empty((rows, stride), dtype=dtype, device=dev)[:, :n]
 
     def _receiver_chunks(self):
         """Receiver indices grouped for ``solve_batch`` under the rules of ``_chunks``."""
@@ -689,7 +713,7 @@ class ReciprocalSensitivity(Sensitivity):
                     estack = self._new_stack(len(mine), n, e.dtype, dev)
                     xstack = self._new_stack(nrec, n, e.dtype, dev)
                     self._stacks[fname] = [estack, xstack]
-                estack[row].copy_(e)
+                estack[row].copy_(e.to(estack.dtype))          # 'single': rounded here, once, on the device
                 del e
             clock = lap('forward', clock)
             meta = Field(grid, frequency=freq)
@@ -717,9 +741,15 @@ class ReciprocalSensitivity(Sensitivity):
                     if field is None:                       # the solve failed: zero field, no contribution
                         xstack[r].zero_()
                     else:
-                        xstack[r].copy_(field[:n])
+                        xstack[r].copy_(field[:n].to(xstack.dtype))
                 del back
             lap('receiver', clock)
+            if self.field_dtype == 'single' and not all(bool(torch.isfinite(t).all()) for t in (estack, xstack)):
+                del self._stacks[fname]
+                raise FloatingPointError(
+                    f"ReciprocalSensitivity: a kept field of frequency {fname!r} ({freq} Hz) is not finite in single "
+                    "precision (an fp64 value beyond 3.4e38, or a solve that diverged); field_dtype='double' keeps the "
+                    "fields as they are solved.")
         self._hier.clear()                   # the inner loop needs no hierarchy
         self._have_forward = True
         return self
@@ -730,16 +760,22 @@ class ReciprocalSensitivity(Sensitivity):
         estack, xstack = self._stacks[fname]
         if self.keep == 'device':
             return estack, xstack
-        rows = [max(len(st[k]) for st in self._stacks.values()) for k in (0, 1)]
-        width = max(st[0].shape[1] for st in self._stacks.values())
         if self._stage is None:
             dev = self._device()
-            self._stage = [torch.empty(rows[k] * width, dtype=estack.dtype, device=dev) for k in (0, 1)]
+            self._stage = [torch.empty(max(len(st[k]) * st[k].stride(0) for st in self._stacks.values()),
+                                       dtype=estack.dtype, device=dev) for k in (0, 1)]
+        return self._upload(self._stage, (estack, xstack))
+
+    @staticmethod
+    def _upload(bufs, hosts):
+        """Pinned stacks into the flat HBM buffers ``bufs``, one contiguous copy each (rows with their padding, which
+        no kernel reads); returns the (rows, n) views with the row stride of the host stacks."""
         out = []
-        for buf, host in zip(self._stage, (estack, xstack)):
-            view = buf[:host.numel()].view(host.shape)
-            view.copy_(host, non_blocking=False)
-            out.append(view)
+        for buf, host in zip(bufs, hosts):
+            rows, stride = len(host), host.stride(0)
+            flat = buf[:rows * stride]
+            flat.copy_(host.as_strided((rows * stride,), (1,), 0), non_blocking=False)
+            out.append(flat.view(rows, stride)[:, :host.shape[1]])
         return out
 
     def _chain_factors(self, dev):
@@ -780,6 +816,12 @@ class ReciprocalSensitivity(Sensitivity):
         # (n_cells, n) in memory = component fastest, then x: the Fortran order of the (n, nx, ny, nz) result
         return torch.stack(list(rows), dim=1).cpu().numpy().reshape(-1).reshape((len(rows),) + shape, order='F')
 
+    @staticmethod
+    def _sp(stack):
+        """Suffix of the C entry points for a stack: ``'_sp'`` for one stored in single precision, else ``''``."""
+        import torch
+        return '_sp' if stack.dtype in (torch.complex64, torch.float32) else ''
+
     def _per_frequency(self):
         """(frequency name, pair indices, grid key, grid, cell volumes, averaging plan, s mu0) per frequency."""
         for fname, freq in self.frequencies.items():
@@ -813,7 +855,7 @@ class ReciprocalSensitivity(Sensitivity):
             n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
             estack, xstack = self._fields_of(fname)
             ns, nr = len(estack), len(xstack)
-            is_complex = int(estack.dtype == torch.complex128)
+            is_complex, sp = int(estack.is_complex()), self._sp(estack)
             w = torch.empty(n, dtype=torch.float64, device=dev)
             _lib.check(L.emg3d_dev_edge_weights(nx, ny, nz, _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(w),
                                                 _ptr(w, o1), _ptr(w, o2), _stream()), 'emg3d_dev_edge_weights')
@@ -823,10 +865,10 @@ class ReciprocalSensitivity(Sensitivity):
             scale = complex(-smu0 / kappa)
             ws_len = L.emg3d_sensitivity_dots_ws_len(ns, nr, n)
             ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
-            res = torch.empty(ns * nr, dtype=estack.dtype, device=dev)
-            _lib.check(L.emg3d_dev_sensitivity_dots(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack),
+            res = torch.empty(ns * nr, dtype=torch.complex128 if is_complex else torch.float64, device=dev)
+            _lib.check(getattr(L, 'emg3d_dev_sensitivity_dots' + sp)(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack),
                                                     xstack.stride(0), nr, _ptr(w), scale.real, scale.imag, _ptr(res),
-                                                    _ptr(ws), ws_len, _stream()), 'emg3d_dev_sensitivity_dots')
+                                                    _ptr(ws), ws_len, _stream()), 'emg3d_dev_sensitivity_dots' + sp)
             res = res.cpu().numpy().reshape(ns, nr)
             for row, i in enumerate(mine):
                 out[self.pairs[i]] = res[row].copy()
@@ -856,12 +898,12 @@ class ReciprocalSensitivity(Sensitivity):
             nx, ny, nz = grid.shape_cells
             n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
             estack, xstack = self._fields_of(fname)
-            is_complex = int(estack.dtype == torch.complex128)
+            is_complex, sp = int(estack.is_complex()), self._sp(estack)
             cdev = torch.from_numpy(coef if is_complex else np.ascontiguousarray(coef.real)).to(dev)
-            t = torch.empty(n, dtype=estack.dtype, device=dev)
-            _lib.check(L.emg3d_dev_sensitivity_combine(n, is_complex, _ptr(estack), estack.stride(0), len(estack),
+            t = torch.empty(n, dtype=torch.complex128 if is_complex else torch.float64, device=dev)
+            _lib.check(getattr(L, 'emg3d_dev_sensitivity_combine' + sp)(n, is_complex, _ptr(estack), estack.stride(0), len(estack),
                                                        _ptr(xstack), xstack.stride(0), len(xstack), _ptr(cdev), _ptr(t),
-                                                       _stream()), 'emg3d_dev_sensitivity_combine')
+                                                       _stream()), 'emg3d_dev_sensitivity_combine' + sp)
             if plan is None:
                 gtarget, nc = grad, ncell
             else:                                          # cell gradient on the computational grid first
@@ -938,10 +980,11 @@ class ReciprocalSensitivity(Sensitivity):
                 continue
             estack, xstack = self._fields_of(fname)
             wdev = torch.from_numpy(np.ascontiguousarray(wf)).to(dev)
-            _lib.check(_lib.lib().emg3d_dev_hessian_diagonal(
-                nx, ny, nz, int(estack.dtype == torch.complex128), _ptr(estack), estack.stride(0), len(estack),
+            name = 'emg3d_dev_hessian_diagonal' + self._sp(estack)
+            _lib.check(getattr(_lib.lib(), name)(
+                nx, ny, nz, int(estack.is_complex()), _ptr(estack), estack.stride(0), len(estack),
                 _ptr(xstack), xstack.stride(0), len(xstack), _ptr(wdev), rx, ry, rz, abs(smu0) ** 2, _ptr(vol), _ptr(h),
-                ncell, _stream()), 'emg3d_dev_hessian_diagonal')
+                ncell, _stream()), name)
         d = self._chain_factors(dev)
         return self._rows_on_host(list(h.view(nrows, ncell) * (d * d)))
 
@@ -1054,7 +1097,7 @@ class ReciprocalSensitivity(Sensitivity):
         try:
             for a, (fa, mine_a, _, _, vol, _, smu0_a) in enumerate(per_freq):
                 ea, xa = self._fields_of(fa)
-                is_complex = int(ea.dtype == torch.complex128)
+                is_complex, name = int(ea.is_complex()), 'emg3d_dev_data_gram' + self._sp(ea)
                 for b in range(a, len(per_freq)):
                     fb, mine_b, _, _, _, _, smu0_b = per_freq[b]
                     if b == a:
@@ -1064,18 +1107,16 @@ class ReciprocalSensitivity(Sensitivity):
                     else:
                         if second is None:
                             second = [torch.empty_like(buf) for buf in self._stage]
-                        eb, xb = (buf[:host.numel()].view(host.shape) for buf, host in zip(second, self._stacks[fb]))
-                        eb.copy_(self._stacks[fb][0])
-                        xb.copy_(self._stacks[fb][1])
+                        eb, xb = self._upload(second, self._stacks[fb])
                     na, nb = len(mine_a) * nrec, len(mine_b) * nrec
                     ws_len = L.emg3d_data_gram_ws_len(nx, ny, nz, is_complex, na, nb)
                     ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
                     blk = torch.empty((c * na, c * nb), dtype=torch.float64, device=dev)
-                    _lib.check(L.emg3d_dev_data_gram(
+                    _lib.check(getattr(L, name)(
                         nx, ny, nz, is_complex, _ptr(ea), ea.stride(0), len(ea), _ptr(xa), xa.stride(0), len(xa),
                         smu0_a.real, smu0_a.imag, _ptr(eb), eb.stride(0), len(eb), _ptr(xb), xb.stride(0), len(xb),
                         smu0_b.real, smu0_b.imag, rx, ry, rz, _ptr(mw), ncell, _ptr(vol), _ptr(blk), c * nb, _ptr(ws),
-                        ws_len, _stream()), 'emg3d_dev_data_gram')
+                        ws_len, _stream()), name)
                     G[rows[a][:, None], rows[b][None, :]] = blk
                     if b != a:
                         G[rows[b][:, None], rows[a][None, :]] = blk.T

@@ -497,6 +497,44 @@ int emg3d_dev_data_gram(int nx, int ny, int nz, int is_complex, const void *e_a,
                         const double *volumes, double *out, size_t ld, double *ws, size_t ws_len,
                         void *stream);
 
+/* ---- kept fields stored in single precision ---------------------------------------
+ * The four products above for stacks that are STORED narrow: elements are complex64 (is_complex: two
+ * floats, re then im) or float32. Each entry takes the argument list of its sibling and returns its
+ * errors with its texts; strides count elements of the narrow type. Only the stacks are narrow. Every
+ * value is widened when it is loaded and every operation, partial sum and result is fp64 as in the
+ * sibling; emg3d_sensitivity_dots_ws_len and emg3d_data_gram_ws_len serve both variants. No atomics,
+ * sums in a fixed order: the same call gives the same bits.
+ *
+ * emg3d_dev_sensitivity_dots_sp: NARROW e, x. fp64: w, scale, out (ns * nr complex128 / float64), ws.
+ * Where e, x and w and both strides are multiples of 16 bytes a lane takes 16 bytes (two complex64 or
+ * four float32, consecutive k) per field and load, otherwise one element; the order of the sum is a
+ * function of the sizes and of that one bit. What lies between n and a stride is never read. */
+int emg3d_dev_sensitivity_dots_sp(size_t n, int is_complex, const void *e, size_t e_stride, int ns,
+                                  const void *x, size_t x_stride, int nr, const double *w,
+                                  double scale_re, double scale_im, void *out, double *ws, size_t ws_len,
+                                  void *stream);
+/* emg3d_dev_sensitivity_combine_sp: NARROW e, x. fp64: coef (ns * nr complex128 / float64) and t (n
+ * complex128 / float64, WRITTEN). 16-byte loads under the rule above (t in the place of w); t does not
+ * depend on which loads are used. */
+int emg3d_dev_sensitivity_combine_sp(size_t n, int is_complex, const void *e, size_t e_stride, int ns,
+                                     const void *x, size_t x_stride, int nr, const void *coef, void *t,
+                                     void *stream);
+/* emg3d_dev_hessian_diagonal_sp: NARROW e, x. fp64: weights, scale, volumes, h. The edges of a patch
+ * are staged in LDS as stored (half the LDS of the sibling) and widened when they are used. */
+int emg3d_dev_hessian_diagonal_sp(int nx, int ny, int nz, int is_complex, const void *e, size_t e_stride,
+                                  int ns, const void *x, size_t x_stride, int nr, const double *weights,
+                                  int row_x, int row_y, int row_z, double scale, const double *volumes,
+                                  double *h, size_t h_stride, void *stream);
+/* emg3d_dev_data_gram_sp: NARROW e_a, x_a, e_b, x_b (both sides). fp64: the scales, model_weights,
+ * volumes, out, ws. Staging as in emg3d_dev_hessian_diagonal_sp; the panels are fp64. */
+int emg3d_dev_data_gram_sp(int nx, int ny, int nz, int is_complex, const void *e_a, size_t e_a_stride,
+                           int ns_a, const void *x_a, size_t x_a_stride, int nr_a, double scale_a_re,
+                           double scale_a_im, const void *e_b, size_t e_b_stride, int ns_b,
+                           const void *x_b, size_t x_b_stride, int nr_b, double scale_b_re,
+                           double scale_b_im, int row_x, int row_y, int row_z,
+                           const double *model_weights, size_t mw_stride, const double *volumes,
+                           double *out, size_t ld, double *ws, size_t ws_len, void *stream);
+
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid
  * (emg3d/models.py:322-366). values (nx,ny,nz) -> out (mx,my,mz), doubles, x fastest. Per axis

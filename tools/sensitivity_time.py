@@ -12,11 +12,18 @@ copy of its byte count. Writes profiles/hessian_diagonal_times.txt. Leg ``gram``
 ``ReciprocalSensitivity.data_gram``, against the route through the existing ``jtvec`` -- 2 N calls on unit data and 1j
 times them, stacked, then ``(Jhat * m) @ Jhat.T`` in NumPy --, taking turns, with one frequency and with two; its kernel
 alone beside a copy of its byte count, and the achieved FMA rate. Writes profiles/data_gram_times.txt.
+``--field-dtype single`` runs the reciprocal, hessian and gram legs on fields kept in single precision.
+Leg ``single``: ``field_dtype='double'`` and ``'single'`` side by side, taking turns in every measurement -- kept bytes,
+the inner iteration, ``hessian_diagonal`` and ``data_gram``, the four kernels alone (HIP events) with the two reductions in
+TB/s on the bytes their stacks hold, and the differences of the five products. Writes
+profiles/reciprocal_single_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
-                                     [--leg all|products|hessian|gram] [--out profiles/sensitivity_times.txt]
+                                     [--leg all|products|hessian|gram|single] [--field-dtype double|single]
+                                     [--out profiles/sensitivity_times.txt]
                                      [--hessian-out profiles/hessian_diagonal_times.txt]
                                      [--gram-out profiles/data_gram_times.txt]
+                                     [--single-out profiles/reciprocal_single_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -54,6 +61,7 @@ def kernel_block(rec, say, launches):
     L = _lib.lib()
     (E, X), = rec._stacks.values()
     ns, nr, n = len(E), len(X), E.shape[1]
+    sp, el = gradient.ReciprocalSensitivity._sp(E), E.element_size()
     dev = E.device
     gen = torch.Generator(device=dev).manual_seed(0)
     w = torch.randn(n, dtype=torch.float64, device=dev, generator=gen)
@@ -62,29 +70,32 @@ def kernel_block(rec, say, launches):
     ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
     out = torch.empty(ns * nr, dtype=torch.complex128, device=dev)
     t = torch.empty(n, dtype=torch.complex128, device=dev)
-    bytes_dots = (ns + nr) * 16 * n + 8 * n                  # every field and w read once
-    bytes_comb = (ns + nr) * 16 * n + 16 * n                 # every field read once, t written
+    bytes_dots = (ns + nr) * el * n + 8 * n                  # every field and w read once
+    bytes_comb = (ns + nr) * el * n + 16 * n                 # every field read once, t written
     src = {b: torch.empty(b // 2, dtype=torch.uint8, device=dev) for b in (bytes_dots, bytes_comb)}
     dst = {b: torch.empty_like(a) for b, a in src.items()}
 
     def k_dots():
-        _lib.check(L.emg3d_dev_sensitivity_dots(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(w), 0.5, -1.5,
-                                                _ptr(out), _ptr(ws), ws_len, _stream()), 'emg3d_dev_sensitivity_dots')
+        _lib.check(getattr(L, 'emg3d_dev_sensitivity_dots' + sp)(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr,
+                                                                 _ptr(w), 0.5, -1.5, _ptr(out), _ptr(ws), ws_len, _stream()),
+                   'emg3d_dev_sensitivity_dots' + sp)
 
     def k_comb():
-        _lib.check(L.emg3d_dev_sensitivity_combine(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(C), _ptr(t),
-                                                   _stream()), 'emg3d_dev_sensitivity_combine')
+        _lib.check(getattr(L, 'emg3d_dev_sensitivity_combine' + sp)(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr,
+                                                                    _ptr(C), _ptr(t), _stream()),
+                   'emg3d_dev_sensitivity_combine' + sp)
     what = [('dots: kernel', k_dots, bytes_dots),
-            ('dots: torch (E * w) @ X.T', lambda: (E * w) @ X.T * (0.5 - 1.5j), bytes_dots),
+            ('dots: torch (E * w) @ X.T', lambda: (Ew * w) @ Xw.T * (0.5 - 1.5j), bytes_dots),
             ('dots: copy', lambda: dst[bytes_dots].copy_(src[bytes_dots]), bytes_dots),
             ('combine: kernel', k_comb, bytes_comb),
-            ('combine: torch ((C @ X) * E).sum(0)', lambda: ((C @ X) * E).sum(0), bytes_comb),
+            ('combine: torch ((C @ X) * E).sum(0)', lambda: ((C @ Xw) * Ew).sum(0), bytes_comb),
             ('combine: copy', lambda: dst[bytes_comb].copy_(src[bytes_comb]), bytes_comb)]
-    ref_d, ref_c = (E * w) @ X.T * (0.5 - 1.5j), ((C @ X) * E).sum(0)
+    Ew, Xw = (E, X) if not sp else (E.to(torch.complex128), X.to(torch.complex128))    # (torch: from fp64 copies)
+    ref_d, ref_c = (Ew * w) @ Xw.T * (0.5 - 1.5j), ((C @ Xw) * Ew).sum(0)
     k_dots()
     k_comb()
-    say(f"kernels alone: n {n:,} edges, ns {ns}, nr {nr}, complex128; algorithmic bytes dots {bytes_dots:,} = (ns + nr) 16 n + "
-        f"8 n, combine {bytes_comb:,} = (ns + nr) 16 n + 16 n; a copy reads half of that count and writes the other half; "
+    say(f"kernels alone: n {n:,} edges, ns {ns}, nr {nr}, {E.dtype}; algorithmic bytes dots {bytes_dots:,} = (ns + nr) {el} n + "
+        f"8 n, combine {bytes_comb:,} = (ns + nr) {el} n + 16 n; a copy reads half of that count and writes the other half; "
         f"kernel vs torch, max-norm relative: dots {float((out.view(ns, nr) - ref_d).abs().max() / ref_d.abs().max()):.1e}, "
         f"combine {float((t - ref_c).abs().max() / ref_c.abs().max()):.1e}")
     del ref_d, ref_c
@@ -157,14 +168,15 @@ def hessian_block(rec, say, repeat, launches):
     vol = rec._computational(rec.pairs[0])[3]
     w = torch.ones(ns * nr, dtype=torch.float64, device=dev)
     h = torch.zeros(nrows * ncell, dtype=torch.float64, device=dev)
-    nbytes = (ns + nr) * 16 * n + 8 * ncell + 16 * nrows * ncell        # every field once, volumes, h read and written
+    sp, el = gradient.ReciprocalSensitivity._sp(E), E.element_size()
+    nbytes = (ns + nr) * el * n + 8 * ncell + 16 * nrows * ncell        # every field once, volumes, h read and written
     src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
     dst = torch.empty_like(src)
 
     def kernel():
-        _lib.check(L.emg3d_dev_hessian_diagonal(nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(w),
-                                                *rows3, 1.0, _ptr(vol), _ptr(h), ncell, _stream()),
-                   'emg3d_dev_hessian_diagonal')
+        _lib.check(getattr(L, 'emg3d_dev_hessian_diagonal' + sp)(nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0),
+                                                                 nr, _ptr(w), *rows3, 1.0, _ptr(vol), _ptr(h), ncell, _stream()),
+                   'emg3d_dev_hessian_diagonal' + sp)
     what = [('hessian_diagonal: kernel', kernel), ('hessian_diagonal: copy', lambda: dst.copy_(src))]
     ms = {name: [] for name, _ in what}
     for rep in range(launches + 3):                  # three warm-up rounds; the candidates take turns
@@ -176,8 +188,8 @@ def hessian_block(rec, say, repeat, launches):
             b.synchronize()
             if rep >= 3:
                 ms[name].append(a.elapsed_time(b))
-    say(f"kernel alone: {nx} x {ny} x {nz} cells, n {n:,} edges, ns {ns}, nr {nr}, complex128, rows {rows3}; algorithmic bytes "
-        f"{nbytes:,} = (ns + nr) 16 n + 8 n_cells + 16 rows n_cells; fp64 FMA ~ 55 ns nr n_cells = {55 * ns * nr * ncell:,}; a copy "
+    say(f"kernel alone: {nx} x {ny} x {nz} cells, n {n:,} edges, ns {ns}, nr {nr}, {E.dtype}, rows {rows3}; algorithmic bytes "
+        f"{nbytes:,} = (ns + nr) {el} n + 8 n_cells + 16 rows n_cells; fp64 FMA ~ 55 ns nr n_cells = {55 * ns * nr * ncell:,}; a copy "
         "reads half of that count and writes the other half")
     for name, _ in what:
         q = np.percentile(ms[name], [50, 25, 75, 0, 100])
@@ -250,14 +262,16 @@ def gram_block(rec, say, repeat, launches, kernel):
     out = torch.empty(M * M, dtype=torch.float64, device=dev)
     ws_len = L.emg3d_data_gram_ws_len(nx, ny, nz, 1, ns * nr, ns * nr)
     ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
-    nbytes = (ns + nr) * 16 * n + 8 * ncell + 8 * nrows * ncell + 16 * ws_len   # fields, volumes, weights; ws written and read
+    sp, el = gradient.ReciprocalSensitivity._sp(E), E.element_size()
+    nbytes = (ns + nr) * el * n + 8 * ncell + 8 * nrows * ncell + 16 * ws_len   # fields, volumes, weights; ws written and read
     src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
     dst = torch.empty_like(src)
 
     def kernel_call():
-        _lib.check(L.emg3d_dev_data_gram(nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, 0.0, 1e-5, _ptr(E),
-                                         E.stride(0), ns, _ptr(X), X.stride(0), nr, 0.0, 1e-5, *rows3, _ptr(mw), ncell, _ptr(vol),
-                                         _ptr(out), M, _ptr(ws), ws_len, _stream()), 'emg3d_dev_data_gram')
+        _lib.check(getattr(L, 'emg3d_dev_data_gram' + sp)(
+            nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, 0.0, 1e-5, _ptr(E), E.stride(0), ns, _ptr(X),
+            X.stride(0), nr, 0.0, 1e-5, *rows3, _ptr(mw), ncell, _ptr(vol), _ptr(out), M, _ptr(ws), ws_len, _stream()),
+            'emg3d_dev_data_gram' + sp)
     what = [('data_gram: kernel (two launches)', kernel_call), ('data_gram: copy', lambda: dst.copy_(src))]
     ms = {name: [] for name, _ in what}
     for rep in range(launches + 3):                  # three warm-up rounds; the candidates take turns
@@ -272,8 +286,8 @@ def gram_block(rec, say, repeat, launches, kernel):
     # rows: 4 edges x 4 FMA per complex product and pair and direction (3 directions in all) + the scaling;
     # update: the full M x M tile per cell and property row (the kernel does not skip the lower triangle)
     fma_rows, fma_full, fma_tri = 55 * ns * nr * ncell, M * M * nrows * ncell, M * (M + 1) // 2 * nrows * ncell
-    say(f"kernel alone: {nx} x {ny} x {nz} cells, n {n:,} edges, ns {ns}, nr {nr}, complex128, rows {rows3}, M {M}; algorithmic "
-        f"bytes {nbytes:,} = (ns + nr) 16 n + 8 n_cells + 8 rows n_cells + 16 ws_len; fp64 FMA: rows of J ~ 55 ns nr n_cells = "
+    say(f"kernel alone: {nx} x {ny} x {nz} cells, n {n:,} edges, ns {ns}, nr {nr}, {E.dtype}, rows {rows3}, M {M}; algorithmic "
+        f"bytes {nbytes:,} = (ns + nr) {el} n + 8 n_cells + 8 rows n_cells + 16 ws_len; fp64 FMA: rows of J ~ 55 ns nr n_cells = "
         f"{fma_rows:,}, update as issued M^2 rows n_cells = {fma_full:,} (one triangle: {fma_tri:,}); a copy reads half of the "
         "byte count and writes the other half")
     for name, _ in what:
@@ -286,19 +300,147 @@ def gram_block(rec, say, repeat, launches, kernel):
         f"{2 * (fma_rows + fma_tri) / med / 1e9:.2f} TFLOP/s")
 
 
+def single_block(recs, say, repeat, launches, v, y):
+    """``recs``: {'double': ..., 'single': ...} after ``forward()``, one frequency. Every measurement lets the two take
+    turns, 'double' first, so that a busy spell of the box hits both."""
+    from emg3d_amd import _lib
+    from emg3d_amd._device import _ptr, _stream
+    L = _lib.lib()
+    names = list(recs)
+
+    def sync():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+    for name, rec in recs.items():
+        (E, X), = rec._stacks.values()
+        say(f"{name:7s} kept_bytes {rec.kept_bytes:,} B ({len(E) + len(X)} fields of {E.shape[1]:,} edges, {E.dtype}, row stride "
+            f"{E.stride(0):,} elements = {E.stride(0) * E.element_size():,} B)")
+    # ---- the methods: inner iteration, hessian_diagonal, data_gram
+    res = {name: {} for name in names}
+    methods = (('jvec', lambda r: r.jvec(v)), ('jtvec', lambda r: r.jtvec(y)), ('hessian_diagonal', lambda r: r.hessian_diagonal()),
+               ('data_gram', lambda r: r.data_gram()))
+    times = {(name, m): [] for name in names for m, _ in methods}
+    for r in range(repeat + 1):                       # run 0: warm-up
+        for name in names:
+            line = f"{name:7s} run {r}{' (warm-up)' if r == 0 else '':10s}:"
+            for m, fn in methods:
+                t0 = sync()
+                res[name][m] = fn(recs[name])
+                t1 = sync()
+                line += f"  {m} {1e3 * (t1 - t0):8.3f}"
+                if r:
+                    times[(name, m)].append(t1 - t0)
+            say(line + " ms")
+    for name in names:
+        t = {m: np.array(times[(name, m)]) for m, _ in methods}
+        it = t['jvec'] + t['jtvec']
+        say(f"mean of {repeat}: {name:7s} inner iteration (jvec + jtvec) {1e3 * it.mean():.3f} ms (fastest {1e3 * it.min():.3f}, "
+            f"slowest {1e3 * it.max():.3f}); hessian_diagonal {1e3 * t['hessian_diagonal'].mean():.3f} ms (fastest "
+            f"{1e3 * t['hessian_diagonal'].min():.3f}); data_gram {1e3 * t['data_gram'].mean():.3f} ms (fastest "
+            f"{1e3 * t['data_gram'].min():.3f}); synchronised, results on the host")
+    # ---- the five products: single against double
+    w1 = {p: np.ones(len(y[p])) for p in y}
+    res['double']['hessian_vec'], res['single']['hessian_vec'] = (recs[k].hessian_vec(v, w1) for k in ('double', 'single'))
+
+    def rel(a, b):
+        if isinstance(a, dict):
+            a, b = np.concatenate([a[k] for k in a]), np.concatenate([b[k] for k in b])
+        return float(np.max(np.abs(a - b)) / np.max(np.abs(b)))
+    say("single against double, max-norm relative difference: " + ", ".join(
+        f"{m} {rel(res['single'][m], res['double'][m]):.2e}" for m in ('jvec', 'jtvec', 'hessian_diagonal', 'hessian_vec', 'data_gram')))
+    # ---- the four kernels alone
+    what = []
+    keep = []                                            # (the buffers of the closures)
+    for name, rec in recs.items():
+        (E, X), = rec._stacks.values()
+        ns, nr, n = len(E), len(X), E.shape[1]
+        sp, el = rec._sp(E), E.element_size()
+        dev = E.device
+        grid = rec.model.grid
+        nx, ny, nz = grid.shape_cells
+        ncell = grid.n_cells
+        rows3 = gradient._EXPAND[rec.model.case]
+        nrows = max(rows3) + 1
+        vol = rec._computational(rec.pairs[0])[3]
+        gen = torch.Generator(device=dev).manual_seed(0)
+        w = torch.randn(n, dtype=torch.float64, device=dev, generator=gen)
+        C = torch.randn(ns, nr, dtype=torch.complex128, device=dev, generator=gen)
+        ws_len = L.emg3d_sensitivity_dots_ws_len(ns, nr, n)
+        ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+        out = torch.empty(ns * nr, dtype=torch.complex128, device=dev)
+        t = torch.empty(n, dtype=torch.complex128, device=dev)
+        wt = torch.ones(ns * nr, dtype=torch.float64, device=dev)
+        h = torch.zeros(nrows * ncell, dtype=torch.float64, device=dev)
+        mw = torch.ones(nrows * ncell, dtype=torch.float64, device=dev)
+        M = 2 * ns * nr
+        gout = torch.empty(M * M, dtype=torch.float64, device=dev)
+        gws_len = L.emg3d_data_gram_ws_len(nx, ny, nz, 1, ns * nr, ns * nr)
+        gws = torch.empty(gws_len, dtype=torch.float64, device=dev)
+        keep.append((w, C, ws, out, t, wt, h, mw, gout, gws))
+        stacks = (ns + nr) * el * n
+
+        def k_dots(E=E, X=X, n=n, ns=ns, nr=nr, w=w, out=out, ws=ws, ws_len=ws_len, sp=sp):
+            _lib.check(getattr(L, 'emg3d_dev_sensitivity_dots' + sp)(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr,
+                                                                     _ptr(w), 0.5, -1.5, _ptr(out), _ptr(ws), ws_len, _stream()),
+                       'emg3d_dev_sensitivity_dots' + sp)
+
+        def k_comb(E=E, X=X, n=n, ns=ns, nr=nr, C=C, t=t, sp=sp):
+            _lib.check(getattr(L, 'emg3d_dev_sensitivity_combine' + sp)(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr,
+                                                                        _ptr(C), _ptr(t), _stream()),
+                       'emg3d_dev_sensitivity_combine' + sp)
+
+        def k_hess(E=E, X=X, ns=ns, nr=nr, wt=wt, h=h, sp=sp):
+            _lib.check(getattr(L, 'emg3d_dev_hessian_diagonal' + sp)(nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X),
+                                                                     X.stride(0), nr, _ptr(wt), *rows3, 1.0, _ptr(vol), _ptr(h),
+                                                                     ncell, _stream()), 'emg3d_dev_hessian_diagonal' + sp)
+
+        def k_gram(E=E, X=X, ns=ns, nr=nr, mw=mw, gout=gout, M=M, gws=gws, gws_len=gws_len, sp=sp):
+            _lib.check(getattr(L, 'emg3d_dev_data_gram' + sp)(
+                nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, 0.0, 1e-5, _ptr(E), E.stride(0), ns, _ptr(X),
+                X.stride(0), nr, 0.0, 1e-5, *rows3, _ptr(mw), ncell, _ptr(vol), _ptr(gout), M, _ptr(gws), gws_len, _stream()),
+                'emg3d_dev_data_gram' + sp)
+        what += [(f'dots {name}', k_dots, stacks), (f'combine {name}', k_comb, stacks), (f'hessian_diagonal {name}', k_hess, stacks),
+                 (f'data_gram {name}', k_gram, stacks)]
+    order = [q for kernel in ('dots', 'combine', 'hessian_diagonal', 'data_gram') for q in what if q[0].split()[0] == kernel]
+    ms = {q[0]: [] for q in order}
+    for rep in range(launches + 3):                  # three warm-up rounds; double and single of a kernel take turns
+        for label, fn, _ in order:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if rep >= 3:
+                ms[label].append(a.elapsed_time(b))
+    say(f"kernels alone on the kept fields (HIP events, {launches} launches each, double and single taking turns); TB/s on the "
+        "bytes the stacks hold, (ns + nr) x n x 16 B or 8 B; dots reads 8 n B of weights besides, combine writes 16 n B")
+    for label, _, nbytes in order:
+        q = np.percentile(ms[label], [50, 25, 75, 0, 100])
+        say(f"  {label:26s} median {q[0]:8.4f} ms (quartiles {q[1]:.4f} .. {q[2]:.4f}, range {q[3]:.4f} .. {q[4]:.4f}) = "
+            f"{nbytes / q[0] / 1e9:7.3f} TB/s on {nbytes:,} B")
+    for kernel in ('dots', 'combine', 'hessian_diagonal', 'data_gram'):
+        d, s1 = (np.median(ms[f'{kernel} {k}']) for k in ('double', 'single'))
+        say(f"  {kernel}: single / double = {s1 / d:.3f} (medians)")
+    del keep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
-    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram'), default='all',
+    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single'), default='all',
                     help="products: the inner iteration four ways and its two reductions; hessian: hessian_diagonal against "
                          "the row-by-row route (needs only the set-up of ReciprocalSensitivity); gram: data_gram against the "
-                         "route through jtvec, one frequency and two (the same set-up, once per survey)")
+                         "route through jtvec, one frequency and two (the same set-up, once per survey); single: "
+                         "field_dtype 'double' and 'single' side by side (not part of 'all')")
+    ap.add_argument('--field-dtype', choices=('double', 'single'), default='double',
+                    help="how ReciprocalSensitivity keeps its fields in the reciprocal, hessian and gram legs")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
     ap.add_argument('--hessian-out', default=os.path.join(ROOT, 'profiles', 'hessian_diagonal_times.txt'))
     ap.add_argument('--gram-out', default=os.path.join(ROOT, 'profiles', 'data_gram_times.txt'))
+    ap.add_argument('--single-out', default=os.path.join(ROOT, 'profiles', 'reciprocal_single_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -313,7 +455,8 @@ def main():
     ncomp = {'isotropic': 1, 'VTI': 2, 'HTI': 2, 'triaxial': 3}[wl['case']]
     v = rng.standard_normal((ncomp,) + tuple(grid.shape_cells))
     y = {(s, 'f'): rng.standard_normal(len(recs)) + 1j * rng.standard_normal(len(recs)) for s in sources}
-    lines = [f"# python tools/sensitivity_time.py --workload {args.workload} --sources {K} --repeat {args.repeat} --leg {args.leg}; box "
+    lines = [f"# python tools/sensitivity_time.py --workload {args.workload} --sources {K} --repeat {args.repeat} --leg {args.leg}"
+             f"{' --field-dtype single' if args.field_dtype == 'single' else ''}; box "
              f"{socket.gethostname()}, {torch.cuda.get_device_name(0)}; commit {commit()}, csrc_sha16 {csrc_sha16()}; "
              f"{time.strftime('%Y-%m-%d')}",
              f"# {wl['label']}; {K} sources x 1 frequency, {len(recs)} receivers; tol 1e-6, tol_gradient 1e-5, "
@@ -346,7 +489,8 @@ def main():
         say(f"one frequency: M = {2 * len(rec.pairs) * len(recs)}, kept {rec.kept_bytes:,} B")
         gram_block(rec, say, args.repeat, args.launches, kernel=True)
         two = gradient.ReciprocalSensitivity(model, sources, {'f': wl['frequency'], 'g': 2 * wl['frequency']}, recs,
-                                             solver_opts=dict(wl['opts'], tol=1e-6), keep='device', batch=K)
+                                             solver_opts=dict(wl['opts'], tol=1e-6), keep='device', batch=K,
+                                             field_dtype=args.field_dtype)
         two.forward()
         say(f"two frequencies ({wl['frequency']} and {2 * wl['frequency']} Hz): M = {2 * len(two.pairs) * len(recs)}, kept "
             f"{two.kept_bytes:,} B; three kernel calls (f-f, f-g, g-g)")
@@ -357,9 +501,24 @@ def main():
             f.write('\n'.join(head + lines[first:]) + '\n')
         del lines[first:]
 
+    if args.leg == 'single':
+        both = {}
+        for name in ('double', 'single'):
+            both[name] = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6),
+                                                        keep='device', batch=K, field_dtype=name)
+            t0 = sync()
+            both[name].forward()
+            say(f"{name:7s} forward(): {1e3 * (sync() - t0):8.1f} ms; {both[name]!r}")
+        single_block(both, say, args.repeat, args.launches, v, y)
+        for rec in both.values():
+            rec.release()
+        os.makedirs(os.path.dirname(os.path.abspath(args.single_out)), exist_ok=True)
+        with open(args.single_out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
     if args.leg in ('hessian', 'gram'):
         rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
-                                             batch=K)
+                                             batch=K, field_dtype=args.field_dtype)
         rec.forward()
         (hessian_leg if args.leg == 'hessian' else gram_leg)(rec)
         rec.release()
@@ -375,7 +534,7 @@ def main():
         say(f"{name:28s} forward(): {1e3 * (t1 - t0):8.1f} ms (the first one builds the hierarchy); {lin!r}")
         setup = t1 - t0              # (of the last variant, keep='device', batch=K: what `reciprocal` is held against)
     rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
-                                         batch=K)
+                                         batch=K, field_dtype=args.field_dtype)
     t0 = sync()
     rec.forward()
     t1 = sync()
