@@ -13,7 +13,7 @@ LIBDIR = os.path.join(_HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libemg3d_amd.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'emg3d_amd.h')
 SOURCES = [os.path.join(CSRC, f) for f in ('kernels.hip', 'stencil.h', 'launch.h', 'cplx.h', 'receivers.h', 'krylov.h',
-                                            'adjoint.h', 'reciprocal.h', 'hessian.h', 'gram.h')] + [HEADER]
+                                            'adjoint.h', 'reciprocal.h', 'hessian.h', 'gram.h', 'block.h')] + [HEADER]
 
 # -ffp-contract: hipcc's own default for HIP, spelled out because csrc/kernels.hip switches contraction off for its
 # line-kernel section and back to THIS mode behind it (`#pragma clang fp contract(fast)`: the pragma can name a mode,
@@ -118,6 +118,14 @@ SIGNATURES = {
     'emg3d_dev_data_gram_sp': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 +
                                [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 + [_ci] * 3 +
                                [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
+    # K vectors per pass over the kept stacks; the _sp siblings take narrow stacks
+    'emg3d_sensitivity_dots_block_ws_len': (_sz, [_ci, _ci, _ci, _sz]),
+    'emg3d_dev_sensitivity_dots_block': (_ci, [_sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci] +
+                                         [ctypes.c_double] * 2 + [_vp, _vp, _sz, _vp]),
+    'emg3d_dev_sensitivity_combine_block': (_ci, [_sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci, _vp, _ci, _vp, _sz, _vp]),
+    'emg3d_dev_sensitivity_dots_block_sp': (_ci, [_sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci] +
+                                            [ctypes.c_double] * 2 + [_vp, _vp, _sz, _vp]),
+    'emg3d_dev_sensitivity_combine_block_sp': (_ci, [_sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci, _vp, _ci, _vp, _sz, _vp]),
     'emg3d_dev_source_field': (_ci, [_ci] * 4 + [_vp] * 7 + [_ci] + [ctypes.c_double] * 2 + [_vp] * 4),
     'emg3d_dev_volume_model': (_ci, [_ci] * 4 + [_vp] * 5 + [_ci] + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp] * 5),
     'emg3d_dev_magnetic_field': (_ci, [_ci] * 4 + [_vp] * 7 + [ctypes.c_double] * 2 + [_vp] * 4),

@@ -2835,3 +2835,4 @@ int emg3d_core_solve(void *amat, void *bvec, int n, int is_complex)
 #include "reciprocal.h"
 #include "hessian.h"
 #include "gram.h"
+#include "block.h"

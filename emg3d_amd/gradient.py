@@ -592,6 +592,12 @@ class ReciprocalSensitivity(Sensitivity):
     Gauss-Newton schemes (``emg3d_dev_data_gram``, DESIGN.md 4.14: the rows of ``J^`` are generated in LDS and consumed
     there, never written), with ``stack_data`` / ``unstack_data`` between data dictionaries and its real vectors.
 
+    Many products at this one linearisation point (randomised SVD, trace estimates, block Krylov methods, probing):
+    ``jvec_block``, ``jtvec_block`` and ``hessian_vec_block`` take K vectors and read the kept fields once per group of
+    ``columns_per_pass`` columns (``emg3d_dev_sensitivity_dots_block`` / ``_combine_block``); a block of
+    model vectors may live on the device -- float64 (K, n, n_cells), cells x fastest, ``to_device`` / ``from_device`` --,
+    and ``hessian_vec_block`` then takes and returns one without anything crossing the host.
+
     field_dtype: ``'double'`` (default) keeps the fields as they are solved, ``n_edges x 16 B`` each. ``'single'``
         keeps them as complex64 (Laplace domain: float32): half the bytes in HBM or pinned memory, over PCIe with
         ``keep='host'``, and through the two HBM-bound products. Only the STORAGE is narrow: a solved
@@ -994,6 +1000,289 @@ class ReciprocalSensitivity(Sensitivity):
         w = self._check_weights(weights)                        # raises before any GPU work, as jvec does for `vector`
         jv = self.jvec(vector)
         return self.jtvec({pair: w[pair] * jv[pair] for pair in jv})
+
+    # ------------------------------------------------------------- blocks of K vectors ---
+    # A block of model vectors on the device: float64 (K, n, n_cells), n as for ``jvec`` (1, 2 or 3), cells x fastest --
+    # what ``jvec`` builds of its vector and ``_rows_on_host`` undoes.
+    def _block_shapes(self):
+        n, shape = _NCOMP[self.model.case], tuple(self.model.grid.shape_cells)
+        return n, shape, [(n,) + shape] + ([shape] if n == 1 else [])
+
+    def _check_vectors(self, vectors):
+        """The NumPy block ``vectors``, K >= 1 model-shaped vectors as ``jvec`` takes them, as (K, n, nx, ny, nz)
+        floats; raises unless it is real and every vector is shaped like the model's properties."""
+        n, shape, allowed = self._block_shapes()
+        v = np.asarray(vectors)
+        if v.ndim < 1 or len(v) < 1 or v.shape[1:] not in allowed or np.iscomplexobj(v):
+            raise ValueError(f"`vectors` must be real with shape (K,) + {' or (K,) + '.join(str(a) for a in allowed[::-1])}, "
+                             f"K >= 1, for a model of case '{self.model.case}'. Provided: {v.dtype} {v.shape}.")
+        return np.asarray(v, dtype=np.float64).reshape((len(v), n) + shape)
+
+    def _check_device_block(self, block, dev=None):
+        """Raises unless the tensor ``block`` is a device block of this instance: float64, (K >= 1, n, n_cells),
+        contiguous, on a HIP device (``dev`` given: on that one)."""
+        import torch
+        n, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
+        if (block.dtype != torch.float64 or block.ndim != 3 or block.shape[0] < 1 or tuple(block.shape[1:]) != (n, ncell) or
+                not block.is_contiguous() or block.device.type != 'cuda' or (dev is not None and block.device != dev)):
+            raise ValueError(f"a device block must be a contiguous float64 tensor of shape (K, {n}, {ncell}), K >= 1, on "
+                             f"the device of the fields{'' if dev is None else f' ({dev})'} for a model of case "
+                             f"'{self.model.case}' (`to_device` builds one). Provided: {block.dtype} {tuple(block.shape)} on "
+                             f"{block.device}, contiguous: {block.is_contiguous()}.")
+        return block
+
+    def _check_block(self, vectors):
+        """``vectors`` of the block methods, validated without a device: (is a device block, the block)."""
+        import torch
+        if isinstance(vectors, torch.Tensor):
+            return True, self._check_device_block(vectors)
+        return False, self._check_vectors(vectors)
+
+    @staticmethod
+    def _check_columns(columns_per_pass):
+        if isinstance(columns_per_pass, bool) or not isinstance(columns_per_pass, (int, np.integer)) or columns_per_pass < 1:
+            raise ValueError(f"`columns_per_pass` must be an integer >= 1. Provided: {columns_per_pass!r}.")
+        return int(columns_per_pass)
+
+    def _upload_block(self, v, dev):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(v)).to(dev).permute(0, 1, 4, 3, 2).reshape(v.shape[0], v.shape[1], -1)
+
+    def to_device(self, vectors):
+        """The NumPy block ``vectors`` -- shape (K,) + a shape that ``jvec`` accepts, real, K >= 1 -- as a device block:
+        float64 (K, n, n_cells) on the device of the fields, n = 1 (isotropic), 2 (HTI, VTI) or 3, cells x fastest.
+        ``from_device`` is its inverse, exactly."""
+        v = self._check_vectors(vectors)                        # raises before any GPU work
+        return self._upload_block(v, self._device())
+
+    def from_device(self, block):
+        """The device block ``block`` as NumPy (K,) + the shape ``jtvec`` returns, every slice laid out like the result
+        of ``jtvec``. ``to_device`` is its inverse, exactly."""
+        self._check_device_block(block)
+        n, shape, _ = self._block_shapes()
+        K, rev = len(block), shape[::-1]
+        if n == 1:
+            return block.cpu().numpy().reshape((K,) + rev).transpose(0, 3, 2, 1)
+        # (K, n_cells, n) in memory = component fastest, then x: the Fortran order of every (n, nx, ny, nz) slice
+        return block.permute(0, 2, 1).contiguous().cpu().numpy().reshape((K,) + rev + (n,)).transpose(0, 4, 3, 2, 1)
+
+    def _block_scratch(self, rows, stride, dtype, dev, what):
+        """(rows, stride) of ``dtype`` in HBM for ``rows`` columns of a pass; raises if that much is not free."""
+        import torch
+        need = rows * stride * torch.empty(0, dtype=dtype).element_size()
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        if need > free:
+            raise MemoryError(f"ReciprocalSensitivity: the {what} of {rows} columns per pass need {need:,} B of HBM, "
+                              f"{free:,} B are free; a smaller `columns_per_pass` needs less.")
+        return torch.empty((rows, stride), dtype=dtype, device=dev)
+
+    def _block_products(self, dev, kc, block=None, data=None, weights=None):
+        """The engine of the three block methods, frequency by frequency with ONE ``_fields_of`` each. ``block``
+        (device block): ``emg3d_dev_edge_weights`` per column and one ``emg3d_dev_sensitivity_dots_block`` per group of
+        at most ``kc`` columns -> jv, dict frequency name -> device tensor (K, ns, nr). Then, with coefficients (K, ns,
+        nr) from ``data`` (list of K data dictionaries: ``conj``, 0 for NaN or a missing pair; columns without a datum
+        at a frequency are left out there, as ``jtvec`` leaves out the frequency) or from ``weights`` (the checked
+        dict: ``conj(weights * jv)``, formed on the device): one ``emg3d_dev_sensitivity_combine_block`` per group and
+        ``emg3d_dev_edges_to_cells`` per column -> the cell gradient (K, 3, n_cells) on the device. Uploads (the weights of
+        all frequencies; ``keep='host'``: a frequency's stacks) and the look at the free HBM come before a frequency's
+        first kernel: between its ``dots_block`` and its ``combine_block`` the host queues torch operations on (K, ns,
+        nr) and waits for nothing. ``data``: the coefficients of a frequency are uploaded before its ``combine_block``."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        L = _lib.lib()
+        nrec, ncell = len(self._rec[0]), self.model.grid.n_cells
+        expand = _EXPAND[self.model.case]
+        K = len(block) if block is not None else len(data)
+        kc = min(kc, K)
+        per_freq = list(self._per_frequency())
+        stride = max(f[3].n_edges for f in per_freq)
+        stride += stride & 1                             # rows of float64 on 16-byte boundaries
+        combine = data is not None or weights is not None
+        wbuf = tbufs = regridded = grad = None
+        if block is not None:
+            wbuf = self._block_scratch(kc, stride, torch.float64, dev, 'edge weights')
+            # the derivative chain of the mapping for the whole block: vector_k * d sigma / d property_k
+            on_model = block * self._chain_factors(dev)
+            regridded = {0: on_model}
+        wdevs = {}
+        if combine:
+            tbufs = {}                                   # field type -> (kc, stride) edge vectors
+            grad = torch.zeros((K, 3, ncell), dtype=torch.float64, device=dev)
+            if weights is not None:
+                # every frequency's weights go up BEFORE the first kernel (an upload from pageable memory waits for the
+                # stream): between dots_block and combine_block there are only torch operations on (K, ns, nr)
+                for fname, mine, *_ in per_freq:
+                    wf = np.stack([weights[self.pairs[i]] for i in mine])
+                    if wf.any():                         # (a frequency whose weights are all zero: as hessian_diagonal)
+                        wdevs[fname] = torch.from_numpy(np.ascontiguousarray(wf)).to(dev)
+        jv = {}
+        for fname, mine, gkey, grid, vol, plan, smu0 in per_freq:
+            if weights is not None and fname not in wdevs:
+                continue
+            coef = None
+            if data is not None:
+                coef = np.zeros((K, len(mine), nrec), dtype=complex)
+                for k, vector in enumerate(data):
+                    for row, i in enumerate(mine):
+                        y = vector.get(self.pairs[i])
+                        if y is not None:
+                            coef[k, row] = np.conj(np.nan_to_num(np.asarray(y, dtype=complex), nan=0.0))
+                active = [k for k in range(K) if coef[k].any()]
+                if not active:
+                    continue
+            nx, ny, nz = grid.shape_cells
+            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
+            estack, xstack = self._fields_of(fname)
+            ns, nr = len(estack), len(xstack)
+            is_complex, sp = int(estack.is_complex()), self._sp(estack)
+            ftype = torch.complex128 if is_complex else torch.float64
+            if combine and ftype not in tbufs:           # (before the kernels: the look at the free HBM is a host call)
+                tbufs[ftype] = self._block_scratch(kc, stride, ftype, dev, 'edge vectors')
+            if block is not None:
+                if gkey not in regridded:        # linear volume average: the map whose adjoint is the way back
+                    regridded[gkey] = torch.stack([torch.stack([plan.on_device(c, log=False) for c in col])
+                                                   for col in on_model])
+                cells = regridded[gkey]
+                kappa = np.conj(1.0 / -smu0) * -smu0             # (as in jvec)
+                scale = complex(-smu0 / kappa)
+                ws_len = L.emg3d_sensitivity_dots_block_ws_len(ns, nr, kc, n)
+                ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+                res = torch.empty((K, ns, nr), dtype=ftype, device=dev)
+                name = 'emg3d_dev_sensitivity_dots_block' + sp
+                for g0 in range(0, K, kc):
+                    g1 = min(g0 + kc, K)
+                    for j in range(g0, g1):
+                        vx, vy, vz = (cells[j, k] for k in expand)
+                        w = wbuf[j - g0]
+                        _lib.check(L.emg3d_dev_edge_weights(nx, ny, nz, _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(w),
+                                                            _ptr(w, o1), _ptr(w, o2), _stream()), 'emg3d_dev_edge_weights')
+                    _lib.check(getattr(L, name)(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack),
+                                                xstack.stride(0), nr, _ptr(wbuf), stride, g1 - g0, scale.real, scale.imag,
+                                                _ptr(res, g0 * ns * nr), _ptr(ws), ws_len, _stream()), name)
+                jv[fname] = res
+            if not combine:
+                continue
+            if coef is not None:
+                cdev = torch.from_numpy(coef if is_complex else np.ascontiguousarray(coef.real)).to(dev)
+            else:
+                cdev = torch.conj_physical(jv[fname] * wdevs[fname]).contiguous()
+                active = list(range(K))
+            tbuf = tbufs[ftype]
+            name = 'emg3d_dev_sensitivity_combine_block' + sp
+            for g0 in range(0, len(active), kc):
+                cols = active[g0:g0 + kc]
+                # the coefficients of the group, contiguous (columns that are left out make gaps)
+                cg = cdev[cols[0]:cols[-1] + 1] if cols[-1] - cols[0] + 1 == len(cols) else cdev[cols].contiguous()
+                _lib.check(getattr(L, name)(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack),
+                                            xstack.stride(0), nr, _ptr(cg), len(cols), _ptr(tbuf), stride, _stream()), name)
+                for row, j in enumerate(cols):
+                    t = tbuf[row]
+                    if plan is None:
+                        gtarget, nc = grad[j].view(-1), ncell
+                    else:                                  # cell gradient on the computational grid first
+                        nc = grid.n_cells
+                        gtarget = torch.zeros(3 * nc, dtype=torch.float64, device=dev)
+                    _lib.check(L.emg3d_dev_edges_to_cells(nx, ny, nz, is_complex, _ptr(t), _ptr(t, o1), _ptr(t, o2),
+                                                          smu0.real, smu0.imag, _ptr(vol), _ptr(gtarget), _ptr(gtarget, nc),
+                                                          _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_edges_to_cells')
+                    if plan is not None:                   # ... and back to the model grid: grad += P^T g
+                        for k in range(3):
+                            plan.adjoint_add(gtarget[k * nc:(k + 1) * nc], grad[j, k])
+        return jv, grad
+
+    def _gradient_block(self, grad):
+        """``_gradient_on_host`` for (K, 3, n_cells), the same operations in the same order, left on the device: the
+        device block (K, n, n_cells) of the model's own properties."""
+        import torch
+        case = self.model.case
+        d = self._chain_factors(grad.device)
+        rows = [grad[:, 0]]
+        if case in ('HTI', 'triaxial'):
+            rows.append(grad[:, 1] * d[1])
+        else:
+            rows[0] = rows[0] + grad[:, 1]
+        if case in ('VTI', 'triaxial'):
+            rows.append(grad[:, 2] * d[-1])
+        else:
+            rows[0] = rows[0] + grad[:, 2]
+        rows[0] = rows[0] * d[0]
+        return torch.stack(rows, dim=1)
+
+    def _data_of(self, jv):
+        """dict frequency name -> device (K, ns, nr) as dict pair -> NumPy (K, n_receivers): the one download."""
+        out = {}
+        for fname, mine, *_ in self._per_frequency():
+            if fname in jv:
+                res = jv[fname].cpu().numpy()
+                for row, i in enumerate(mine):
+                    out[self.pairs[i]] = res[:, row].copy()
+        return {p: out[p] for p in self.pairs if p in out}
+
+    def jvec_block(self, vectors, columns_per_pass=8):
+        """``jvec`` for a block of K model vectors in one pass over the kept fields: dict (src, freq) -> complex array
+        (K, n_receivers), real in the Laplace domain; row ``k`` is what ``jvec(vectors[k])`` returns (the sums run in
+        another order: equal to rounding).
+
+        ``vectors``: a NumPy block, shape (K,) + a shape ``jvec`` accepts, or a device block (``to_device``: float64
+        (K, n, n_cells) on the device of the fields, cells x fastest); K >= 1. Per frequency the stacks are fetched once
+        (``keep='host'``: ONE upload for the block), the derivative chain is one product on the block, then per group
+        of at most ``columns_per_pass`` columns one ``emg3d_dev_edge_weights`` per column and one
+        ``emg3d_dev_sensitivity_dots_block``; scratch: ``columns_per_pass x n_edges x 8 B``, allocated
+        once per call (``MemoryError`` if that is not free). The only download is the result. No solve: ``n_solves``
+        does not move."""
+        kc = self._check_columns(columns_per_pass)
+        on_dev, block = self._check_block(vectors)              # raises on a wrong block, before any GPU work
+        dev = self._device()
+        self.forward()
+        block = self._check_device_block(block, dev) if on_dev else self._upload_block(block, dev)
+        return self._data_of(self._block_products(dev, kc, block=block)[0])
+
+    def _check_data_block(self, data):
+        if isinstance(data, dict) or not hasattr(data, '__len__') or len(data) < 1:
+            raise ValueError("`data` must be a sequence of K >= 1 data dictionaries (src, freq) -> (n_receivers,) values, "
+                             f"as `jtvec` takes them. Provided: {type(data).__name__}"
+                             f"{'' if isinstance(data, dict) or not hasattr(data, '__len__') else ' of length 0'}.")
+        data = list(data)
+        for vector in data:
+            self._check_data(vector)
+        return data
+
+    def jtvec_block(self, data, on_device=False, columns_per_pass=8):
+        """``jtvec`` for K data sets in one pass over the kept fields: NumPy (K,) + the shape ``jtvec`` returns, slice
+        ``k`` the bits of ``jtvec(data[k])``; ``on_device=True``: the device block (K, n, n_cells) instead (see
+        ``jvec_block``; ``from_device`` converts it), nothing is downloaded.
+
+        ``data``: a sequence of K >= 1 data dictionaries as ``jtvec`` takes them (NaN or a missing pair: no datum). Per
+        frequency the stacks are fetched once, then per group of at most ``columns_per_pass`` columns one
+        ``emg3d_dev_sensitivity_combine_block`` and one ``emg3d_dev_edges_to_cells`` per column; the anisotropy
+        bookkeeping and the derivative chain run on the block. Scratch: ``columns_per_pass x n_edges x 16 B`` (Laplace
+        domain: 8 B), allocated once per call (``MemoryError`` if that is not free). No solve."""
+        kc = self._check_columns(columns_per_pass)
+        data = self._check_data_block(data)                     # raises before any GPU work
+        dev = self._device()
+        self.forward()
+        out = self._gradient_block(self._block_products(dev, kc, data=data)[1])
+        return out if on_device else self.from_device(out)
+
+    def hessian_vec_block(self, vectors, weights=None, on_device=None, columns_per_pass=8):
+        """``hessian_vec`` for a block of K model vectors, ``J^H W J`` applied to every column, with the data left on the
+        device: per frequency the stacks are fetched once, ``emg3d_dev_sensitivity_dots_block`` gives jv (K, ns, nr),
+        the coefficients ``conj(weights * jv)`` are formed there and go straight into
+        ``emg3d_dev_sensitivity_combine_block`` -- no download, no upload and no wait between the two halves.
+
+        ``vectors``: as for ``jvec_block``; a device block gives a device block (``on_device=None``), a NumPy block
+        NumPy as ``jtvec_block`` returns it; ``on_device`` True / False decides otherwise. ``weights``: as for
+        ``hessian_diagonal``. Slice ``k`` equals ``hessian_vec(vectors[k], weights)`` to rounding. Scratch: both of
+        ``jvec_block`` and ``jtvec_block``."""
+        kc = self._check_columns(columns_per_pass)
+        w = self._check_weights(weights)                        # raises before any GPU work, as do the next two
+        on_dev, block = self._check_block(vectors)
+        dev = self._device()
+        self.forward()
+        block = self._check_device_block(block, dev) if on_dev else self._upload_block(block, dev)
+        out = self._gradient_block(self._block_products(dev, kc, block=block, weights=w)[1])
+        return out if (on_dev if on_device is None else on_device) else self.from_device(out)
 
     # ------------------------------------------------------- data-space normal matrix ---
     def _data_rows(self):

@@ -535,6 +535,48 @@ int emg3d_dev_data_gram_sp(int nx, int ny, int nz, int is_complex, const void *e
                            const double *model_weights, size_t mw_stride, const double *volumes,
                            double *out, size_t ld, double *ws, size_t ws_len, void *stream);
 
+/* ---- block sensitivity products: nv vectors per pass over the kept stacks ----------
+ * emg3d_dev_sensitivity_dots and emg3d_dev_sensitivity_combine for nv >= 1 vectors at once; stacks,
+ * strides and types as there. A field value is loaded once for all the vectors of a tile (csrc/block.h).
+ * Plain fp64, no atomics, every sum in an order fixed by the sizes alone: the same call gives the same
+ * bits. Sizes beyond one launch are refused with EMG3D_ERR_BADARG.
+ *
+ * out[(v * ns + s) * nr + r] = scale * sum_k w_v[k] e_s[k] x_r[k] (out: device, nv * ns * nr elements of
+ * the fields' type, written). w: nv rows of n doubles, row v starts v * w_stride doubles behind row 0,
+ * w_stride >= n (what lies between n and w_stride is never read). A wave streams 4096 consecutive k for
+ * a tile of 2 x 4 (s, r) and 4 vectors: the products e_s[k] x_r[k] are formed once per k and added into
+ * the accumulators of the 4 vectors, in registers; the up to 8 waves of a workgroup take different tiles
+ * of the same k, so that a field value comes from HBM once. Reduced in the wave and across workgroups
+ * through ws (doubles, at least emg3d_sensitivity_dots_block_ws_len(ns, nr, nv, n) of them; 0: bad
+ * sizes) in a second launch. Equal to emg3d_dev_sensitivity_dots per vector up to the order of the sums
+ * (nv = 1 runs that kernel). */
+size_t emg3d_sensitivity_dots_block_ws_len(int ns, int nr, int nv, size_t n);
+int emg3d_dev_sensitivity_dots_block(size_t n, int is_complex, const void *e, size_t e_stride, int ns,
+                                     const void *x, size_t x_stride, int nr, const double *w,
+                                     size_t w_stride, int nv, double scale_re, double scale_im, void *out,
+                                     double *ws, size_t ws_len, void *stream);
+/* t_v[k] = sum_s e_s[k] * (sum_r coef[(v * ns + s) * nr + r] * x_r[k]), r first, then s, both ascending:
+ * the operations of emg3d_dev_sensitivity_combine term by term, so row v of t is bit-identical to its
+ * result with the coefficients coef + v * ns * nr. t: nv rows of n elements of the fields' type, WRITTEN,
+ * row v starts v * t_stride elements behind row 0, t_stride >= n (what lies between the rows is not
+ * touched). coef: device, nv * ns * nr elements. One thread per k keeps its receiver values and loads
+ * every e_s[k] once for up to 8 vectors; more vectors: one pass over the stacks per 8 (nv = 1 runs the
+ * kernel of emg3d_dev_sensitivity_combine). */
+int emg3d_dev_sensitivity_combine_block(size_t n, int is_complex, const void *e, size_t e_stride, int ns,
+                                        const void *x, size_t x_stride, int nr, const void *coef, int nv,
+                                        void *t, size_t t_stride, void *stream);
+/* The two for stacks stored in single precision (conventions of the _sp entry points above): NARROW e, x;
+ * fp64: w, scale, out, ws, coef, t. 16-byte loads where every row of both stacks and of w (of t) starts on
+ * a 16-byte boundary, element-wise loads otherwise; t does not depend on which are used. */
+int emg3d_dev_sensitivity_dots_block_sp(size_t n, int is_complex, const void *e, size_t e_stride, int ns,
+                                        const void *x, size_t x_stride, int nr, const double *w,
+                                        size_t w_stride, int nv, double scale_re, double scale_im,
+                                        void *out, double *ws, size_t ws_len, void *stream);
+int emg3d_dev_sensitivity_combine_block_sp(size_t n, int is_complex, const void *e, size_t e_stride,
+                                           int ns, const void *x, size_t x_stride, int nr,
+                                           const void *coef, int nv, void *t, size_t t_stride,
+                                           void *stream);
+
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid
  * (emg3d/models.py:322-366). values (nx,ny,nz) -> out (mx,my,mz), doubles, x fastest. Per axis

@@ -17,13 +17,19 @@ Leg ``single``: ``field_dtype='double'`` and ``'single'`` side by side, taking t
 the inner iteration, ``hessian_diagonal`` and ``data_gram``, the four kernels alone (HIP events) with the two reductions in
 TB/s on the bytes their stacks hold, and the differences of the five products. Writes
 profiles/reciprocal_single_times.txt.
+Leg ``block``: K vectors per pass over the kept fields, K = 1, 2, 4, 8, 16, for ``field_dtype='double'``
+and ``'single'`` -- the two block kernels alone against K launches of the single-vector kernels (HIP events, taking turns in an order drawn anew for every round;
+TB/s on the bytes the stacks hold plus the w / t rows), then ``hessian_vec_block`` on a device block, result left on the
+device, against K calls of ``hessian_vec`` on NumPy vectors, with ``keep='device'`` and ``keep='host'``. Writes
+profiles/block_products_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
-                                     [--leg all|products|hessian|gram|single] [--field-dtype double|single]
+                                     [--leg all|products|hessian|gram|single|block] [--field-dtype double|single]
                                      [--out profiles/sensitivity_times.txt]
                                      [--hessian-out profiles/hessian_diagonal_times.txt]
                                      [--gram-out profiles/data_gram_times.txt]
                                      [--single-out profiles/reciprocal_single_times.txt]
+                                     [--block-out profiles/block_products_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -424,23 +430,137 @@ def single_block(recs, say, repeat, launches, v, y):
     del keep
 
 
+BLOCK_K = (1, 2, 4, 8, 16)
+
+
+def block_kernels(rec, say, launches):
+    """``emg3d_dev_sensitivity_dots_block`` / ``_combine_block`` with K vectors against K launches of
+    ``emg3d_dev_sensitivity_dots`` / ``_combine`` on the kept fields of ``rec`` (one frequency, ``keep='device'``)."""
+    from emg3d_amd import _lib
+    from emg3d_amd._device import _ptr, _stream
+    L = _lib.lib()
+    (E, X), = rec._stacks.values()
+    ns, nr, n = len(E), len(X), E.shape[1]
+    sp, el = rec._sp(E), E.element_size()
+    dev = E.device
+    kmax = max(BLOCK_K)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(kmax, n, dtype=torch.float64, device=dev, generator=gen)
+    C = torch.randn(kmax, ns, nr, dtype=torch.complex128, device=dev, generator=gen)
+    T = torch.empty(kmax, n, dtype=torch.complex128, device=dev)
+    out = torch.empty(kmax * ns * nr, dtype=torch.complex128, device=dev)
+    ws_len = L.emg3d_sensitivity_dots_block_ws_len(ns, nr, kmax, n)
+    ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+    one_len = L.emg3d_sensitivity_dots_ws_len(ns, nr, n)
+    stacks = (ns + nr) * el * n
+    names = {k: 'emg3d_dev_sensitivity_' + k + sp for k in ('dots', 'combine', 'dots_block', 'combine_block')}
+
+    def dots_block(K):
+        _lib.check(getattr(L, names['dots_block'])(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(W), n, K, 0.5,
+                                                   -1.5, _ptr(out), _ptr(ws), ws_len, _stream()), names['dots_block'])
+
+    def dots_each(K):
+        for k in range(K):
+            _lib.check(getattr(L, names['dots'])(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(W, k * n), 0.5,
+                                                 -1.5, _ptr(out, k * ns * nr), _ptr(ws), one_len, _stream()), names['dots'])
+
+    def combine_block(K):
+        _lib.check(getattr(L, names['combine_block'])(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(C), K,
+                                                      _ptr(T), n, _stream()), names['combine_block'])
+
+    def combine_each(K):
+        for k in range(K):
+            _lib.check(getattr(L, names['combine'])(n, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr,
+                                                    _ptr(C, k * ns * nr), _ptr(T, k * n), _stream()), names['combine'])
+    # the two routes give the same numbers (dots: to rounding; combine: the same bits)
+    dots_block(kmax)
+    a = out.clone()
+    combine_block(kmax)
+    b = T.clone()
+    dots_each(kmax)
+    combine_each(kmax)
+    say(f"kernels alone: n {n:,} edges, ns {ns}, nr {nr}, {E.dtype}; K = {kmax}: dots_block vs {kmax} x dots, max-norm relative "
+        f"{float((a - out).abs().max() / out.abs().max()):.1e}; combine_block vs {kmax} x combine bit-identical: "
+        f"{bool(torch.equal(b, T))}. Bytes: block = stacks {stacks:,} + K rows (w: 8 n, t: 16 n); K launches = K x (stacks + one "
+        f"row). fp64 FMA per edge: dots_block ns nr (4 + 2 K), K x dots 6 ns nr K (complex); HIP events around the K launches, "
+        f"the candidates taking turns in an order drawn anew for every round, {launches} timed rounds after 3 warm-up rounds")
+    del a, b
+    for K in BLOCK_K:
+        what = [(f'dots_block K={K}', lambda K=K: dots_block(K), stacks + 8 * n * K),
+                (f'{K} x dots', lambda K=K: dots_each(K), K * (stacks + 8 * n)),
+                (f'combine_block K={K}', lambda K=K: combine_block(K), stacks + 16 * n * K),
+                (f'{K} x combine', lambda K=K: combine_each(K), K * (stacks + 16 * n))]
+        ms = {name: [] for name, _, _ in what}
+        shuffle = np.random.default_rng(K)           # a new order every round: neither a candidate's position nor its
+        for rep in range(launches + 3):              # predecessor (whose traffic is what the caches hold) stays the same
+            for name, fn, _ in [what[i] for i in shuffle.permutation(len(what))]:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if rep >= 3:
+                    ms[name].append(e0.elapsed_time(e1))
+        q = {name: np.percentile(ms[name], [50, 25, 75]) for name in ms}
+        for name, _, nbytes in what:
+            say(f"  {name:22s} median {q[name][0]:8.4f} ms (quartiles {q[name][1]:.4f} .. {q[name][2]:.4f}) = "
+                f"{nbytes / q[name][0] / 1e9:7.3f} TB/s on {nbytes:,} B")
+        for blk, each, ceil in ((what[0][0], what[1][0], K * (stacks + 8 * n) / (stacks + 8 * n * K)),
+                                (what[2][0], what[3][0], K * (stacks + 16 * n) / (stacks + 16 * n * K))):
+            spread = max(q[blk][2] - q[blk][1], q[each][2] - q[each][1])
+            say(f"  {each} / {blk}: {q[each][0] / q[blk][0]:.2f} x (medians; ceiling of the byte count {ceil:.2f} x); difference "
+                f"{q[each][0] - q[blk][0]:+.4f} ms, larger quartile spread {spread:.4f} ms")
+
+
+def block_methods(rec, say, repeat, label):
+    """``hessian_vec_block`` on a device block, the result left on the device, against K calls of ``hessian_vec`` on NumPy
+    vectors (the only route without the block methods), taking turns; all weights one."""
+    grid = rec.model.grid
+    ncomp = gradient._NCOMP[rec.model.case]
+    rng = np.random.default_rng(1)
+
+    def sync():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+    for K in BLOCK_K:
+        V = rng.standard_normal((K, ncomp) + tuple(grid.shape_cells))
+        B = rec.to_device(V)
+        tb, te = [], []
+        for r in range(repeat + 1):                     # run 0: warm-up
+            t0 = sync()
+            H = rec.hessian_vec_block(B)
+            t1 = sync()
+            R = [rec.hessian_vec(v) for v in V]
+            t2 = sync()
+            if r:
+                tb.append(t1 - t0)
+                te.append(t2 - t1)
+        diff = float(np.max(np.abs(rec.from_device(H) - np.stack(R))) / np.max(np.abs(np.stack(R))))
+        say(f"  {label}, K = {K:2d}: hessian_vec_block (device block in and out, columns_per_pass 8) mean {1e3 * np.mean(tb):9.3f} ms "
+            f"(fastest {1e3 * min(tb):9.3f}); {K} x hessian_vec (NumPy in and out) mean {1e3 * np.mean(te):9.3f} ms (fastest "
+            f"{1e3 * min(te):9.3f}); ratio of the means {np.mean(te) / np.mean(tb):6.1f}; max-norm relative difference {diff:.1e}")
+        del H, R, B
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
-    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single'), default='all',
+    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block'), default='all',
                     help="products: the inner iteration four ways and its two reductions; hessian: hessian_diagonal against "
                          "the row-by-row route (needs only the set-up of ReciprocalSensitivity); gram: data_gram against the "
                          "route through jtvec, one frequency and two (the same set-up, once per survey); single: "
-                         "field_dtype 'double' and 'single' side by side (not part of 'all')")
+                         "field_dtype 'double' and 'single' side by side (not part of 'all'); block: K vectors per pass, the "
+                         "block kernels and hessian_vec_block against K single calls (not part of 'all')")
     ap.add_argument('--field-dtype', choices=('double', 'single'), default='double',
                     help="how ReciprocalSensitivity keeps its fields in the reciprocal, hessian and gram legs")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
     ap.add_argument('--hessian-out', default=os.path.join(ROOT, 'profiles', 'hessian_diagonal_times.txt'))
     ap.add_argument('--gram-out', default=os.path.join(ROOT, 'profiles', 'data_gram_times.txt'))
     ap.add_argument('--single-out', default=os.path.join(ROOT, 'profiles', 'reciprocal_single_times.txt'))
+    ap.add_argument('--block-out', default=os.path.join(ROOT, 'profiles', 'block_products_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -514,6 +634,27 @@ def main():
             rec.release()
         os.makedirs(os.path.dirname(os.path.abspath(args.single_out)), exist_ok=True)
         with open(args.single_out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
+    if args.leg == 'block':
+        for name in ('double', 'single'):
+            kw = dict(solver_opts=dict(wl['opts'], tol=1e-6), batch=K, field_dtype=name)
+            rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, keep='device', **kw)
+            rec.forward()
+            say(f"field_dtype='{name}': {rec!r}")
+            block_kernels(rec, say, args.launches)
+            say(f"methods, field_dtype='{name}' (wall time, synchronised, mean of {args.repeat} after a warm-up run, the two routes "
+                "taking turns):")
+            block_methods(rec, say, args.repeat, "keep='device'")
+            rec.release()
+            del rec
+            host = gradient.ReciprocalSensitivity(model, sources, freqs, recs, keep='host', **kw)
+            host.forward()
+            block_methods(host, say, args.repeat, "keep='host'  ")
+            host.release()
+            del host
+        os.makedirs(os.path.dirname(os.path.abspath(args.block_out)), exist_ok=True)
+        with open(args.block_out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
         return
     if args.leg in ('hessian', 'gram'):
