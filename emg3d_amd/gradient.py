@@ -268,13 +268,23 @@ class Sensitivity:
         _lib.require_gpu()
         return torch.device('cuda', torch.cuda.current_device())
 
+    def _grid_of(self, pair):
+        """The computational grid of a pair; the model's own grid object where ``grids`` gives none or an equal one."""
+        g = self.grids.get(pair) if isinstance(self.grids, dict) else self.grids
+        return self.model.grid if g is None or g == self.model.grid else g
+
+    def _require_model_grid(self, what, why):
+        """Raises for the product ``what`` unless every pair is computed on the model grid."""
+        for pair in self.pairs:
+            if self._grid_of(pair) is not self.model.grid:
+                raise NotImplementedError(f"{what}: the computational grid of {pair!r} (`grids`) is not the model grid; "
+                                          f"there every row of the sensitivity needs its own adjoint volume average {why}.")
+
     def _computational(self, pair):
         """(grid key, grid, model on it, cell volumes in HBM, averaging plan or None) of a pair."""
         import torch
         mgrid = self.model.grid
-        g = self.grids.get(pair) if isinstance(self.grids, dict) else self.grids
-        if g is None or g == mgrid:
-            g = mgrid
+        g = self._grid_of(pair)
         key = id(g) if g is not mgrid else 0
         if key not in self._on_grid:
             vol = torch.from_numpy(np.ascontiguousarray(g.cell_volumes, dtype=np.float64)).to(self._device())
@@ -357,12 +367,16 @@ class Sensitivity:
             local = {k: v for part in parts for k, v in part.items()}
         return {p: local[p] for p in self.pairs if p in local}
 
+    def _may_batch(self):
+        """Whether solves may go through ``solve_batch`` (the rules of ``batch`` in the class docstring)."""
+        return (self.batch > 1 and not self._mag.any() and
+                self.opts.get('sslsolver', True) in (True, False, None, 'bicgstab') and
+                self.opts.get('cycle', 'F') is not None)
+
     def _chunks(self):
         """This rank's pairs in solve order, grouped for ``solve_batch``: lists of up to ``batch`` pair indices
         that share frequency and computational grid (lists of one: pair by pair)."""
-        batched = (self.batch > 1 and not self._mag.any() and
-                   self.opts.get('sslsolver', True) in (True, False, None, 'bicgstab') and
-                   self.opts.get('cycle', 'F') is not None)
+        batched = self._may_batch()
         chunks = []
         for i in self._order:
             key = (self.pairs[i][1], self._computational(self.pairs[i])[0])
@@ -465,16 +479,43 @@ class Sensitivity:
             return synthetic - obs, w
         return self._back_propagate(data, with_misfit=True)
 
+    def _solve_residual_sources(self, gkey, gmodel, meta, rfields, opts):
+        """The solutions for the residual source fields ``rfields`` of one frequency and grid, one ``solve`` or one
+        ``solve_batch``: a list of (field in HBM -- ``None``: the solve failed --, solver info). The field of a single
+        source is the hierarchy's own ``top.e``: the next solve overwrites it."""
+        from emg3d_amd import solver
+        hier = self._hierarchy(gkey, gmodel, meta, len(rfields))
+        if len(rfields) == 1:
+            _, info = solver.solve(gmodel, rfields[0], return_info=True, always_return=True, hierarchy=hier,
+                                   _download=False, _sparse_source=True, **opts)
+            return [(hier.top.e, info)]
+        for rf in rfields:
+            rf._trust_sparse = True
+        res = solver.solve_batch(gmodel, rfields, keep_fields=False, hierarchy=hier, _device_fields=True, **opts)
+        return [(info.pop('_device_field', None), info) for _, info in res]
+
+    @staticmethod
+    def _on_model_grid(plan, grid, target, launch):
+        """``launch(gtarget, nc)`` adds a cell gradient to the three rows of ``nc`` cells at ``gtarget``: into ``target``,
+        (3, n_cells) on the model grid, at once, or (``plan``: the averaging plan of another computational ``grid``) on
+        that grid first and from there through the adjoint of the linear volume average, target += P^T g."""
+        import torch
+        if plan is None:
+            return launch(target.view(-1), target.shape[1])
+        nc = grid.n_cells
+        gtarget = torch.zeros(3 * nc, dtype=torch.float64, device=target.device)
+        launch(gtarget, nc)
+        for k in range(3):
+            plan.adjoint_add(gtarget[k * nc:(k + 1) * nc], target[k])
+
     def _back_propagate(self, data, with_misfit=False):
         """``data(pair, synthetic) -> (residual, weight)`` per receiver: steps 3-8 of the module docstring for
         this rank's pairs. Returns (misfit of the residuals if asked for, gradient)."""
         import torch
-        from emg3d_amd import _lib, parallel, solver
+        from emg3d_amd import _lib, parallel
         from emg3d_amd._device import _ptr, _stream
         dev = self._device()
-        mgrid = self.model.grid
-        ncell = mgrid.n_cells
-        grad = torch.zeros(3 * ncell, dtype=torch.float64, device=dev)
+        grad = torch.zeros((3, self.model.grid.n_cells), dtype=torch.float64, device=dev)
         misfit = 0.0
         opts = {**self.opts, 'tol': self.tol_gradient}
         for chunk in self._chunks():
@@ -502,42 +543,22 @@ class Sensitivity:
             if not live:
                 continue
             meta = Field(grid, frequency=freq)
-            if len(live) == 1:
-                hier = self._hierarchy(gkey, gmodel, meta)
-                _, binfo = solver.solve(gmodel, rfields[live[0]], return_info=True, always_return=True, hierarchy=hier,
-                                        _download=False, _sparse_source=True, **opts)
-                back = {live[0]: (hier.top.e, binfo)}
-            else:
-                for b in live:
-                    rfields[b]._trust_sparse = True
-                hier = self._hierarchy(gkey, gmodel, meta, len(live))
-                res = solver.solve_batch(gmodel, [rfields[b] for b in live], keep_fields=False, hierarchy=hier,
-                                         _device_fields=True, **opts)
-                back = {b: (info['_device_field'], info) for b, (_, info) in zip(live, res)}
-            top = hier.top
+            back = self._solve_residual_sources(gkey, gmodel, meta, [rfields[b] for b in live], opts)
             smu0 = complex(meta.smu0)
             o1, o2 = grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
-            for b in live:
-                bfield, binfo = back[b]
+            for b, (bfield, binfo) in zip(live, back):
                 self.n_solves['jtvec'] += 1
-                binfo.pop('_device_field', None)
                 self.info.setdefault(self.pairs[chunk[b]], {})['backward'] = binfo
                 if bfield is None:                         # the solve failed: zero field, no contribution
                     continue
                 e_fwd = forward[b]
-                if plan is None:
-                    gtarget, nc = grad, ncell
-                else:                                          # cell gradient on the computational grid first
-                    nc = grid.n_cells
-                    gtarget = torch.empty(3 * nc, dtype=torch.float64, device=dev)
-                    _lib.check(_lib.lib().emg3d_dev_zero(_ptr(gtarget), gtarget.numel() * 8, _stream()), 'emg3d_dev_zero')
-                _lib.check(_lib.lib().emg3d_dev_gradient_accumulate(
-                    nx, ny, nz, int(top.is_complex), _ptr(e_fwd), _ptr(e_fwd, o1), _ptr(e_fwd, o2),
-                    _ptr(bfield), _ptr(bfield, o1), _ptr(bfield, o2), smu0.real, smu0.imag, _ptr(vol),
-                    _ptr(gtarget), _ptr(gtarget, nc), _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_gradient_accumulate')
-                if plan is not None:                           # ... and back to the model grid: grad += P^T g
-                    for k in range(3):
-                        plan.adjoint_add(gtarget[k * nc:(k + 1) * nc], grad[k * ncell:(k + 1) * ncell])
+
+                def accumulate(gtarget, nc):
+                    _lib.check(_lib.lib().emg3d_dev_gradient_accumulate(
+                        nx, ny, nz, int(bfield.is_complex()), _ptr(e_fwd), _ptr(e_fwd, o1), _ptr(e_fwd, o2),
+                        _ptr(bfield), _ptr(bfield, o1), _ptr(bfield, o2), smu0.real, smu0.imag, _ptr(vol),
+                        _ptr(gtarget), _ptr(gtarget, nc), _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_gradient_accumulate')
+                self._on_model_grid(plan, grid, grad, accumulate)
             del forward, back
         # the one collective of the path: sum over the ranks
         tm = torch.tensor([misfit], dtype=torch.float64, device=dev)
@@ -554,10 +575,7 @@ class Sensitivity:
     def _gradient_on_host(self, grad):
         """The cell gradient with respect to the three conductivity components (device, 3 x n_cells, x fastest) as
         the model-shaped array of the model's own properties (step 8 of the module docstring)."""
-        mgrid = self.model.grid
-        ncell = mgrid.n_cells
-        g3 = np.stack([grad[k * ncell:(k + 1) * ncell].cpu().numpy().reshape(mgrid.shape_cells, order='F')
-                       for k in range(3)])
+        g3 = np.stack([row.cpu().numpy().reshape(self.model.grid.shape_cells, order='F') for row in grad])
         return _finish_gradient(self.model, g3)
 
 
@@ -573,8 +591,9 @@ class ReciprocalSensitivity(Sensitivity):
         jvec(v)[s, r] = conj(-s mu0) sum_k w_k e_s[k] x_r[k]         w = cells_to_edges(volumes * v), real
         jtvec(y)      = cells(real(s mu0 t)),    t[k] = sum_s e_s[k] sum_r conj(y[s, r]) x_r[k]
 
-    -- reductions over the kept fields, bound by HBM (``emg3d_dev_edge_weights`` + ``emg3d_dev_sensitivity_dots``;
-    ``emg3d_dev_sensitivity_combine`` + ``emg3d_dev_edges_to_cells``): no solve, no hierarchy and no receiver
+    -- reductions over the kept fields, bound by HBM (``emg3d_dev_edge_weights`` + ``emg3d_dev_sensitivity_dots_block``;
+    ``emg3d_dev_sensitivity_combine_block`` + ``emg3d_dev_edges_to_cells``; one column runs the single-vector kernels
+    ``k_sensitivity_dots`` / ``k_sensitivity_combine``): no solve, no hierarchy and no receiver
     interpolation in a Gauss-Newton inner iteration. The price: ``n_receivers`` more solves per frequency in
     ``forward()`` (batched by ``solve_batch`` under the rules of ``Sensitivity``'s ``batch``) and their fields.
 
@@ -624,11 +643,9 @@ class ReciprocalSensitivity(Sensitivity):
         if self.world > 1:
             raise NotImplementedError("ReciprocalSensitivity runs in one process; sharding frequencies over the ranks "
                                       f"of a process group (here: {self.world}) is not implemented.")
-        mgrid = self.model.grid
         shared = {}
         for sname, fname in self.pairs:
-            g = self.grids.get((sname, fname)) if isinstance(self.grids, dict) else self.grids
-            g = mgrid if g is None or g == mgrid else g
+            g = self._grid_of((sname, fname))
             first = shared.setdefault(fname, g)
             if not (g is first or g == first):
                 raise ValueError(f"ReciprocalSensitivity: all pairs of frequency {fname!r} must share one computational "
@@ -681,10 +698,7 @@ class ReciprocalSensitivity(Sensitivity):
     def _receiver_chunks(self):
         """Receiver indices grouped for ``solve_batch`` under the rules of ``_chunks``."""
         nrec = len(self._rec[0])
-        batched = (self.batch > 1 and not self._mag.any() and
-                   self.opts.get('sslsolver', True) in (True, False, None, 'bicgstab') and
-                   self.opts.get('cycle', 'F') is not None)
-        step = self.batch if batched else 1
+        step = self.batch if self._may_batch() else 1
         return [list(range(r, min(r + step, nrec))) for r in range(0, nrec, step)]
 
     def forward(self):
@@ -694,7 +708,6 @@ class ReciprocalSensitivity(Sensitivity):
             return self
         import time
         import torch
-        from emg3d_amd import solver
         dev = self._device()
         nrec = len(self._rec[0])
 
@@ -729,18 +742,7 @@ class ReciprocalSensitivity(Sensitivity):
                     unit = np.full(nrec, np.nan, dtype=complex)
                     unit[r] = 1.0
                     rfields.append(residual_source_field(grid, freq, self.receivers, unit, np.ones(nrec), self._mag))
-                if len(chunk) == 1:
-                    hier = self._hierarchy(gkey, gmodel, meta)
-                    _, info = solver.solve(gmodel, rfields[0], return_info=True, always_return=True, hierarchy=hier,
-                                           _download=False, _sparse_source=True, **opts)
-                    back = [(hier.top.e, info)]
-                else:
-                    for rf in rfields:
-                        rf._trust_sparse = True
-                    hier = self._hierarchy(gkey, gmodel, meta, len(chunk))
-                    res = solver.solve_batch(gmodel, rfields, keep_fields=False, hierarchy=hier, _device_fields=True,
-                                             **opts)
-                    back = [(info.pop('_device_field', None), info) for _, info in res]
+                back = self._solve_residual_sources(gkey, gmodel, meta, rfields, opts)
                 for r, (field, info) in zip(chunk, back):
                     self.n_solves['receiver'] += 1
                     self.info[('receiver', r, fname)] = info
@@ -795,38 +797,17 @@ class ReciprocalSensitivity(Sensitivity):
                  for name in _PROPS[self.model.case]], dev))
         return self._dchain
 
-    def _gradient_on_host(self, grad):
-        """``Sensitivity._gradient_on_host`` with the bookkeeping of ``_finish_gradient`` (same order) on the device:
-        only the model's own components cross to the host, laid out as the result."""
-        case = self.model.case
-        g = grad.view(3, -1)
-        d = self._chain_factors(grad.device)
-        rows = [g[0]]
-        if case in ('HTI', 'triaxial'):
-            rows.append(g[1] * d[1])
-        else:
-            rows[0] = rows[0] + g[1]
-        if case in ('VTI', 'triaxial'):
-            rows.append(g[2] * d[-1])
-        else:
-            rows[0] = rows[0] + g[2]
-        rows[0] = rows[0] * d[0]
-        return self._rows_on_host(rows)
-
-    def _rows_on_host(self, rows):
-        """One device row of n_cells (x fastest) per property of the model as the model-shaped host array."""
-        import torch
-        shape = tuple(self.model.grid.shape_cells)
-        if len(rows) == 1:
-            return rows[0].cpu().numpy().reshape(shape, order='F')
-        # (n_cells, n) in memory = component fastest, then x: the Fortran order of the (n, nx, ny, nz) result
-        return torch.stack(list(rows), dim=1).cpu().numpy().reshape(-1).reshape((len(rows),) + shape, order='F')
-
     @staticmethod
     def _sp(stack):
         """Suffix of the C entry points for a stack: ``'_sp'`` for one stored in single precision, else ``''``."""
         import torch
         return '_sp' if stack.dtype in (torch.complex64, torch.float32) else ''
+
+    def _entry(self, name, stack):
+        """(the C entry point ``name`` for the storage type of ``stack``, its full name for ``_lib.check``)."""
+        from emg3d_amd import _lib
+        name += self._sp(stack)
+        return getattr(_lib.lib(), name), name
 
     def _per_frequency(self):
         """(frequency name, pair indices, grid key, grid, cell volumes, averaging plan, s mu0) per frequency."""
@@ -838,90 +819,25 @@ class ReciprocalSensitivity(Sensitivity):
 
     # ------------------------------------------------------------------------------- jvec ---
     def jvec(self, vector):
-        """As ``Sensitivity.jvec``, without a solve: per frequency one ``emg3d_dev_edge_weights`` and one
-        ``emg3d_dev_sensitivity_dots`` over the kept fields."""
-        import torch
-        from emg3d_amd import _lib
-        from emg3d_amd._device import _ptr, _stream
+        """As ``Sensitivity.jvec``, without a solve: a block of one column through ``_block_products`` -- per frequency
+        one ``emg3d_dev_edge_weights`` and one ``emg3d_dev_sensitivity_dots_block``, which runs the single-vector kernel
+        for one column."""
         v = _check_vector(self.model, vector)                   # raises on a wrong shape, before any GPU work
         dev = self._device()
         self.forward()
-        expand = _EXPAND[self.model.case]
-        # the derivative chain of the mapping on the device: vector_k * d sigma / d property_k, cells x fastest
-        vdev = torch.from_numpy(np.ascontiguousarray(v)).to(dev).permute(0, 3, 2, 1).reshape(len(v), -1)
-        on_model = list(vdev * self._chain_factors(dev))
-        regridded = {0: on_model}
-        L = _lib.lib()
-        out = {}
-        for fname, mine, gkey, grid, vol, plan, smu0 in self._per_frequency():
-            if gkey not in regridded:            # linear volume average: the map whose adjoint is jtvec's way back
-                regridded[gkey] = [plan.on_device(c, log=False) for c in on_model]
-            vx, vy, vz = (regridded[gkey][k] for k in expand)
-            nx, ny, nz = grid.shape_cells
-            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
-            estack, xstack = self._fields_of(fname)
-            ns, nr = len(estack), len(xstack)
-            is_complex, sp = int(estack.is_complex()), self._sp(estack)
-            w = torch.empty(n, dtype=torch.float64, device=dev)
-            _lib.check(L.emg3d_dev_edge_weights(nx, ny, nz, _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(w),
-                                                _ptr(w, o1), _ptr(w, o2), _stream()), 'emg3d_dev_edge_weights')
-            # unit residual at a receiver: point source of strength conj(1 / (-s mu0)), times -s mu0 as every source
-            # (residual_source_field) = kappa p_r; jvec = p_r^T A^-1 (-s mu0 w e_s) = -s mu0 / kappa sum w e_s x_r
-            kappa = np.conj(1.0 / -smu0) * -smu0
-            scale = complex(-smu0 / kappa)
-            ws_len = L.emg3d_sensitivity_dots_ws_len(ns, nr, n)
-            ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
-            res = torch.empty(ns * nr, dtype=torch.complex128 if is_complex else torch.float64, device=dev)
-            _lib.check(getattr(L, 'emg3d_dev_sensitivity_dots' + sp)(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack),
-                                                    xstack.stride(0), nr, _ptr(w), scale.real, scale.imag, _ptr(res),
-                                                    _ptr(ws), ws_len, _stream()), 'emg3d_dev_sensitivity_dots' + sp)
-            res = res.cpu().numpy().reshape(ns, nr)
-            for row, i in enumerate(mine):
-                out[self.pairs[i]] = res[row].copy()
-        return {p: out[p] for p in self.pairs if p in out}
+        jv = self._data_of(self._block_products(dev, 1, block=self._upload_block(v[None], dev))[0])
+        return {pair: rows[0] for pair, rows in jv.items()}
 
     # ------------------------------------------------------------------------------ jtvec ---
     def jtvec(self, vector):
-        """As ``Sensitivity.jtvec``, without a solve: per frequency one ``emg3d_dev_sensitivity_combine`` with the
-        coefficients ``conj(vector)`` (0 for NaN or a missing pair) and one ``emg3d_dev_edges_to_cells``."""
-        import torch
-        from emg3d_amd import _lib
-        from emg3d_amd._device import _ptr, _stream
-        nrec = self._check_data(vector)
+        """As ``Sensitivity.jtvec``, without a solve: one data set through ``_block_products`` -- per frequency one
+        ``emg3d_dev_sensitivity_combine_block``, which runs the single-vector kernel for one column, with the
+        coefficients ``conj(vector)`` (0 for NaN or a missing pair) and one ``emg3d_dev_edges_to_cells``; the anisotropy
+        bookkeeping and the derivative chain on the device, only the model's own components cross to the host."""
+        self._check_data(vector)
         dev = self._device()
         self.forward()
-        ncell = self.model.grid.n_cells
-        grad = torch.zeros(3 * ncell, dtype=torch.float64, device=dev)
-        L = _lib.lib()
-        for fname, mine, gkey, grid, vol, plan, smu0 in self._per_frequency():
-            coef = np.zeros((len(mine), nrec), dtype=complex)
-            for row, i in enumerate(mine):
-                y = vector.get(self.pairs[i])
-                if y is not None:
-                    coef[row] = np.conj(np.nan_to_num(np.asarray(y, dtype=complex), nan=0.0))
-            if not coef.any():
-                continue
-            nx, ny, nz = grid.shape_cells
-            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
-            estack, xstack = self._fields_of(fname)
-            is_complex, sp = int(estack.is_complex()), self._sp(estack)
-            cdev = torch.from_numpy(coef if is_complex else np.ascontiguousarray(coef.real)).to(dev)
-            t = torch.empty(n, dtype=torch.complex128 if is_complex else torch.float64, device=dev)
-            _lib.check(getattr(L, 'emg3d_dev_sensitivity_combine' + sp)(n, is_complex, _ptr(estack), estack.stride(0), len(estack),
-                                                       _ptr(xstack), xstack.stride(0), len(xstack), _ptr(cdev), _ptr(t),
-                                                       _stream()), 'emg3d_dev_sensitivity_combine' + sp)
-            if plan is None:
-                gtarget, nc = grad, ncell
-            else:                                          # cell gradient on the computational grid first
-                nc = grid.n_cells
-                gtarget = torch.zeros(3 * nc, dtype=torch.float64, device=dev)
-            _lib.check(L.emg3d_dev_edges_to_cells(nx, ny, nz, is_complex, _ptr(t), _ptr(t, o1), _ptr(t, o2), smu0.real,
-                                                  smu0.imag, _ptr(vol), _ptr(gtarget), _ptr(gtarget, nc),
-                                                  _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_edges_to_cells')
-            if plan is not None:                           # ... and back to the model grid: grad += P^T g
-                for k in range(3):
-                    plan.adjoint_add(gtarget[k * nc:(k + 1) * nc], grad[k * ncell:(k + 1) * ncell])
-        return self._gradient_on_host(grad)
+        return self.from_device(self._gradient_block(self._block_products(dev, 1, data=[vector])[1]))[0]
 
     def misfit_and_gradient(self, observed, weights=None):
         """Misfit ``sum w |synthetic - observed|^2 / 2`` from the kept responses and its gradient
@@ -967,18 +883,12 @@ class ReciprocalSensitivity(Sensitivity):
         from emg3d_amd import _lib
         from emg3d_amd._device import _ptr, _stream
         w = self._check_weights(weights)                        # raises before any GPU work
-        mgrid = self.model.grid
-        for pair in self.pairs:
-            g = self.grids.get(pair) if isinstance(self.grids, dict) else self.grids
-            if not (g is None or g == mgrid):
-                raise NotImplementedError(
-                    f"hessian_diagonal: the computational grid of {pair!r} (`grids`) is not the model grid; there every "
-                    "row of the sensitivity needs its own adjoint volume average before the modulus is taken.")
+        self._require_model_grid('hessian_diagonal', 'before the modulus is taken')
         dev = self._device()
         self.forward()
         rx, ry, rz = _EXPAND[self.model.case]
-        nrows, ncell = _NCOMP[self.model.case], mgrid.n_cells
-        nx, ny, nz = mgrid.shape_cells
+        nrows, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
+        nx, ny, nz = self.model.grid.shape_cells
         h = torch.zeros(nrows * ncell, dtype=torch.float64, device=dev)
         for fname, mine, gkey, grid, vol, plan, smu0 in self._per_frequency():
             wf = np.stack([w[self.pairs[i]] for i in mine])
@@ -986,13 +896,13 @@ class ReciprocalSensitivity(Sensitivity):
                 continue
             estack, xstack = self._fields_of(fname)
             wdev = torch.from_numpy(np.ascontiguousarray(wf)).to(dev)
-            name = 'emg3d_dev_hessian_diagonal' + self._sp(estack)
-            _lib.check(getattr(_lib.lib(), name)(
+            kernel, name = self._entry('emg3d_dev_hessian_diagonal', estack)
+            _lib.check(kernel(
                 nx, ny, nz, int(estack.is_complex()), _ptr(estack), estack.stride(0), len(estack),
                 _ptr(xstack), xstack.stride(0), len(xstack), _ptr(wdev), rx, ry, rz, abs(smu0) ** 2, _ptr(vol), _ptr(h),
                 ncell, _stream()), name)
         d = self._chain_factors(dev)
-        return self._rows_on_host(list(h.view(nrows, ncell) * (d * d)))
+        return self.from_device(h.view(1, nrows, ncell) * (d * d))[0]
 
     def hessian_vec(self, vector, weights=None):
         """Gauss-Newton Hessian times a model-shaped real ``vector``: ``jtvec({pair: weights[pair] * jvec(vector)[pair]})``,
@@ -1003,7 +913,7 @@ class ReciprocalSensitivity(Sensitivity):
 
     # ------------------------------------------------------------- blocks of K vectors ---
     # A block of model vectors on the device: float64 (K, n, n_cells), n as for ``jvec`` (1, 2 or 3), cells x fastest --
-    # what ``jvec`` builds of its vector and ``_rows_on_host`` undoes.
+    # ``jvec`` and ``jtvec`` are the products of a block of one.
     def _block_shapes(self):
         n, shape = _NCOMP[self.model.case], tuple(self.model.grid.shape_cells)
         return n, shape, [(n,) + shape] + ([shape] if n == 1 else [])
@@ -1071,17 +981,18 @@ class ReciprocalSensitivity(Sensitivity):
         import torch
         need = rows * stride * torch.empty(0, dtype=dtype).element_size()
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        if need > free:
+        if need > free:                                  # (one column, as for jvec / jtvec: nothing smaller to advise)
             raise MemoryError(f"ReciprocalSensitivity: the {what} of {rows} columns per pass need {need:,} B of HBM, "
-                              f"{free:,} B are free; a smaller `columns_per_pass` needs less.")
+                              f"{free:,} B are free" + ("; a smaller `columns_per_pass` needs less." if rows > 1 else "."))
         return torch.empty((rows, stride), dtype=dtype, device=dev)
 
     def _block_products(self, dev, kc, block=None, data=None, weights=None):
-        """The engine of the three block methods, frequency by frequency with ONE ``_fields_of`` each. ``block``
+        """The engine of ``jvec`` and ``jtvec`` (a block of one column, ``kc`` = 1) and of the three block methods,
+        frequency by frequency with ONE ``_fields_of`` each. ``block``
         (device block): ``emg3d_dev_edge_weights`` per column and one ``emg3d_dev_sensitivity_dots_block`` per group of
         at most ``kc`` columns -> jv, dict frequency name -> device tensor (K, ns, nr). Then, with coefficients (K, ns,
         nr) from ``data`` (list of K data dictionaries: ``conj``, 0 for NaN or a missing pair; columns without a datum
-        at a frequency are left out there, as ``jtvec`` leaves out the frequency) or from ``weights`` (the checked
+        at a frequency are left out there, a frequency without any is skipped) or from ``weights`` (the checked
         dict: ``conj(weights * jv)``, formed on the device): one ``emg3d_dev_sensitivity_combine_block`` per group and
         ``emg3d_dev_edges_to_cells`` per column -> the cell gradient (K, 3, n_cells) on the device. Uploads (the weights of
         all frequencies; ``keep='host'``: a frequency's stacks) and the look at the free HBM come before a frequency's
@@ -1135,21 +1046,23 @@ class ReciprocalSensitivity(Sensitivity):
             n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
             estack, xstack = self._fields_of(fname)
             ns, nr = len(estack), len(xstack)
-            is_complex, sp = int(estack.is_complex()), self._sp(estack)
+            is_complex = int(estack.is_complex())
             ftype = torch.complex128 if is_complex else torch.float64
-            if combine and ftype not in tbufs:           # (before the kernels: the look at the free HBM is a host call)
+            if combine and ftype not in tbufs:          # (before the kernels: the look at the free HBM is a host call)
                 tbufs[ftype] = self._block_scratch(kc, stride, ftype, dev, 'edge vectors')
             if block is not None:
                 if gkey not in regridded:        # linear volume average: the map whose adjoint is the way back
                     regridded[gkey] = torch.stack([torch.stack([plan.on_device(c, log=False) for c in col])
                                                    for col in on_model])
                 cells = regridded[gkey]
-                kappa = np.conj(1.0 / -smu0) * -smu0             # (as in jvec)
+                # unit residual at a receiver: point source of strength conj(1 / (-s mu0)), times -s mu0 as every source
+                # (residual_source_field) = kappa p_r; jvec = p_r^T A^-1 (-s mu0 w e_s) = -s mu0 / kappa sum w e_s x_r
+                kappa = np.conj(1.0 / -smu0) * -smu0
                 scale = complex(-smu0 / kappa)
                 ws_len = L.emg3d_sensitivity_dots_block_ws_len(ns, nr, kc, n)
                 ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
                 res = torch.empty((K, ns, nr), dtype=ftype, device=dev)
-                name = 'emg3d_dev_sensitivity_dots_block' + sp
+                dots, name = self._entry('emg3d_dev_sensitivity_dots_block', estack)
                 for g0 in range(0, K, kc):
                     g1 = min(g0 + kc, K)
                     for j in range(g0, g1):
@@ -1157,9 +1070,9 @@ class ReciprocalSensitivity(Sensitivity):
                         w = wbuf[j - g0]
                         _lib.check(L.emg3d_dev_edge_weights(nx, ny, nz, _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(w),
                                                             _ptr(w, o1), _ptr(w, o2), _stream()), 'emg3d_dev_edge_weights')
-                    _lib.check(getattr(L, name)(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack),
-                                                xstack.stride(0), nr, _ptr(wbuf), stride, g1 - g0, scale.real, scale.imag,
-                                                _ptr(res, g0 * ns * nr), _ptr(ws), ws_len, _stream()), name)
+                    _lib.check(dots(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack), xstack.stride(0), nr,
+                                    _ptr(wbuf), stride, g1 - g0, scale.real, scale.imag, _ptr(res, g0 * ns * nr), _ptr(ws),
+                                    ws_len, _stream()), name)
                 jv[fname] = res
             if not combine:
                 continue
@@ -1169,31 +1082,27 @@ class ReciprocalSensitivity(Sensitivity):
                 cdev = torch.conj_physical(jv[fname] * wdevs[fname]).contiguous()
                 active = list(range(K))
             tbuf = tbufs[ftype]
-            name = 'emg3d_dev_sensitivity_combine_block' + sp
+            combine_block, name = self._entry('emg3d_dev_sensitivity_combine_block', estack)
             for g0 in range(0, len(active), kc):
                 cols = active[g0:g0 + kc]
                 # the coefficients of the group, contiguous (columns that are left out make gaps)
                 cg = cdev[cols[0]:cols[-1] + 1] if cols[-1] - cols[0] + 1 == len(cols) else cdev[cols].contiguous()
-                _lib.check(getattr(L, name)(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack),
-                                            xstack.stride(0), nr, _ptr(cg), len(cols), _ptr(tbuf), stride, _stream()), name)
+                _lib.check(combine_block(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack), xstack.stride(0), nr,
+                                         _ptr(cg), len(cols), _ptr(tbuf), stride, _stream()), name)
                 for row, j in enumerate(cols):
                     t = tbuf[row]
-                    if plan is None:
-                        gtarget, nc = grad[j].view(-1), ncell
-                    else:                                  # cell gradient on the computational grid first
-                        nc = grid.n_cells
-                        gtarget = torch.zeros(3 * nc, dtype=torch.float64, device=dev)
-                    _lib.check(L.emg3d_dev_edges_to_cells(nx, ny, nz, is_complex, _ptr(t), _ptr(t, o1), _ptr(t, o2),
-                                                          smu0.real, smu0.imag, _ptr(vol), _ptr(gtarget), _ptr(gtarget, nc),
-                                                          _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_edges_to_cells')
-                    if plan is not None:                   # ... and back to the model grid: grad += P^T g
-                        for k in range(3):
-                            plan.adjoint_add(gtarget[k * nc:(k + 1) * nc], grad[j, k])
+
+                    def to_cells(gtarget, nc):
+                        _lib.check(L.emg3d_dev_edges_to_cells(
+                            nx, ny, nz, is_complex, _ptr(t), _ptr(t, o1), _ptr(t, o2), smu0.real, smu0.imag, _ptr(vol),
+                            _ptr(gtarget), _ptr(gtarget, nc), _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_edges_to_cells')
+                    self._on_model_grid(plan, grid, grad[j], to_cells)
         return jv, grad
 
     def _gradient_block(self, grad):
-        """``_gradient_on_host`` for (K, 3, n_cells), the same operations in the same order, left on the device: the
-        device block (K, n, n_cells) of the model's own properties."""
+        """The bookkeeping of ``_finish_gradient``, the same operations in the same order, for the cell gradients (K, 3,
+        n_cells) on the device: the device block (K, n, n_cells) of the model's own properties, of which ``from_device``
+        downloads only those components, laid out as the result."""
         import torch
         case = self.model.case
         d = self._chain_factors(grad.device)
@@ -1359,20 +1268,14 @@ class ReciprocalSensitivity(Sensitivity):
         from emg3d_amd import _lib
         from emg3d_amd._device import _ptr, _stream
         m = self._check_model_weights(model_weights)            # raises before any GPU work
-        mgrid = self.model.grid
-        for pair in self.pairs:
-            g = self.grids.get(pair) if isinstance(self.grids, dict) else self.grids
-            if not (g is None or g == mgrid):
-                raise NotImplementedError(
-                    f"data_gram: the computational grid of {pair!r} (`grids`) is not the model grid; there every row "
-                    "of the sensitivity needs its own adjoint volume average before the product is taken.")
+        self._require_model_grid('data_gram', 'before the product is taken')
         c = self._data_rows()
         dev = self._device()
         self.forward()
         L = _lib.lib()
         rx, ry, rz = _EXPAND[self.model.case]
-        ncell = mgrid.n_cells
-        nx, ny, nz = mgrid.shape_cells
+        ncell = self.model.grid.n_cells
+        nx, ny, nz = self.model.grid.shape_cells
         nrec = len(self._rec[0])
         n = len(self.pairs) * nrec
         d = self._chain_factors(dev)
@@ -1386,7 +1289,8 @@ class ReciprocalSensitivity(Sensitivity):
         try:
             for a, (fa, mine_a, _, _, vol, _, smu0_a) in enumerate(per_freq):
                 ea, xa = self._fields_of(fa)
-                is_complex, name = int(ea.is_complex()), 'emg3d_dev_data_gram' + self._sp(ea)
+                is_complex = int(ea.is_complex())
+                kernel, name = self._entry('emg3d_dev_data_gram', ea)
                 for b in range(a, len(per_freq)):
                     fb, mine_b, _, _, _, _, smu0_b = per_freq[b]
                     if b == a:
@@ -1401,7 +1305,7 @@ class ReciprocalSensitivity(Sensitivity):
                     ws_len = L.emg3d_data_gram_ws_len(nx, ny, nz, is_complex, na, nb)
                     ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
                     blk = torch.empty((c * na, c * nb), dtype=torch.float64, device=dev)
-                    _lib.check(getattr(L, name)(
+                    _lib.check(kernel(
                         nx, ny, nz, is_complex, _ptr(ea), ea.stride(0), len(ea), _ptr(xa), xa.stride(0), len(xa),
                         smu0_a.real, smu0_a.imag, _ptr(eb), eb.stride(0), len(eb), _ptr(xb), xb.stride(0), len(xb),
                         smu0_b.real, smu0_b.imag, rx, ry, rz, _ptr(mw), ncell, _ptr(vol), _ptr(blk), c * nb, _ptr(ws),
