@@ -1432,8 +1432,9 @@ def test_magnetic_field_and_receivers_vs_reference_vectors(golden_receivers):
 
 
 def test_spline_and_linear_device_kernels_vs_scipy():
-    """The device spline prefilter / evaluation and the trilinear kernel against SciPy itself on a
-    96 x 70 x 50 array (complex and real), coordinates up to and beyond the edges."""
+    """The device spline prefilter and the spline evaluation against SciPy itself on a 96 x 70 x 50
+    array (complex and real), coordinates up to and beyond the edges. The trilinear kernel is not
+    called here: test_pre_post_kernels.py::test_linear_eval_kernel_vs_scipy calls it directly."""
     import scipy.ndimage as ndi
     from emg3d_amd._device import _ptr, _stream
     rng = np.random.default_rng(3)
