@@ -13,7 +13,8 @@ LIBDIR = os.path.join(_HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libemg3d_amd.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'emg3d_amd.h')
 SOURCES = [os.path.join(CSRC, f) for f in ('kernels.hip', 'stencil.h', 'launch.h', 'cplx.h', 'receivers.h', 'krylov.h',
-                                            'adjoint.h', 'reciprocal.h', 'hessian.h', 'gram.h', 'block.h')] + [HEADER]
+                                            'adjoint.h', 'reciprocal.h', 'hessian.h', 'gram.h', 'block.h',
+                                            'regularise.h')] + [HEADER]
 
 # -ffp-contract: hipcc's own default for HIP, spelled out because csrc/kernels.hip switches contraction off for its
 # line-kernel section and back to THIS mode behind it (`#pragma clang fp contract(fast)`: the pragma can name a mode,
@@ -126,6 +127,16 @@ SIGNATURES = {
     'emg3d_dev_sensitivity_dots_block_sp': (_ci, [_sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci] +
                                             [ctypes.c_double] * 2 + [_vp, _vp, _sz, _vp]),
     'emg3d_dev_sensitivity_combine_block_sp': (_ci, [_sz, _ci, _vp, _sz, _ci, _vp, _sz, _ci, _vp, _ci, _vp, _sz, _vp]),
+    # the inner solve of a Gauss-Newton step: regulariser and block PCG
+    'emg3d_model_regulariser_ws_len': (_sz, [_ci] * 5),
+    'emg3d_dev_model_regulariser': (_ci, [_ci] * 3 + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp, _ci, _ci, _vp, _vp,
+                                          ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
+    'emg3d_dev_model_regulariser_diagonal': (_ci, [_ci] * 3 + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp, _vp, _vp]),
+    'emg3d_pcg_table_len': (_sz, [_ci]),
+    'emg3d_pcg_ws_len': (_sz, [_sz, _ci]),
+    'emg3d_dev_pcg_update': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 10 + [_sz, _vp]),
+    'emg3d_dev_pcg_scalar': (_ci, [_sz, _ci, _ci, ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
+    'emg3d_dev_pcg_direction': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 7),
     'emg3d_dev_source_field': (_ci, [_ci] * 4 + [_vp] * 7 + [_ci] + [ctypes.c_double] * 2 + [_vp] * 4),
     'emg3d_dev_volume_model': (_ci, [_ci] * 4 + [_vp] * 5 + [_ci] + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp] * 5),
     'emg3d_dev_magnetic_field': (_ci, [_ci] * 4 + [_vp] * 7 + [ctypes.c_double] * 2 + [_vp] * 4),

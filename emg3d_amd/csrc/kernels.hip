@@ -2836,3 +2836,4 @@ int emg3d_core_solve(void *amat, void *bvec, int n, int is_complex)
 #include "hessian.h"
 #include "gram.h"
 #include "block.h"
+#include "regularise.h"

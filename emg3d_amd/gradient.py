@@ -617,6 +617,13 @@ class ReciprocalSensitivity(Sensitivity):
     model vectors may live on the device -- float64 (K, n, n_cells), cells x fastest, ``to_device`` / ``from_device`` --,
     and ``hessian_vec_block`` then takes and returns one without anything crossing the host.
 
+    Their consumer, the inner linear solve of a Gauss-Newton step: ``gauss_newton_solve`` solves ``(Re(J^H W J) + lambda_k
+    R) x_k = b_k`` for K dampings at once by preconditioned CG on the device -- the K columns share every
+    ``hessian_vec_block`` pass, the rest of an iteration is three fused kernels, the per-column scalars stay in a device
+    table (``emg3d_dev_model_regulariser``, ``emg3d_dev_pcg_update`` / ``_scalar`` / ``_direction``, DESIGN.md 4.17);
+    ``regulariser_vec_block`` applies the smallness-plus-roughness operator ``R`` on its own. The outer inversion loop
+    (line search, observed data, choice of the damping) is the user's.
+
     field_dtype: ``'double'`` (default) keeps the fields as they are solved, ``n_edges x 16 B`` each. ``'single'``
         keeps them as complex64 (Laplace domain: float32): half the bytes in HBM or pinned memory, over PCIe with
         ``keep='host'``, and through the two HBM-bound products. Only the STORAGE is narrow: a solved
@@ -660,6 +667,7 @@ class ReciprocalSensitivity(Sensitivity):
         self._stacks = {}            # frequency name -> [source fields (ns x n), receiver fields (nr x n)]
         self._stage = None           # keep='host': the staging pair in HBM
         self._dchain = None
+        self._widths = None          # the model grid's cell widths in HBM (regulariser)
 
     def __repr__(self):
         ns, nr, nf = len(self.sources), len(self._rec[0]), len(self.frequencies)
@@ -886,6 +894,13 @@ class ReciprocalSensitivity(Sensitivity):
         self._require_model_grid('hessian_diagonal', 'before the modulus is taken')
         dev = self._device()
         self.forward()
+        return self.from_device(self._hessian_diagonal_block(w, dev))[0]
+
+    def _hessian_diagonal_block(self, w, dev):
+        """``hessian_diagonal`` for the checked weights ``w`` as a device block of one column, (1, n, n_cells)."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
         rx, ry, rz = _EXPAND[self.model.case]
         nrows, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
         nx, ny, nz = self.model.grid.shape_cells
@@ -902,7 +917,7 @@ class ReciprocalSensitivity(Sensitivity):
                 _ptr(xstack), xstack.stride(0), len(xstack), _ptr(wdev), rx, ry, rz, abs(smu0) ** 2, _ptr(vol), _ptr(h),
                 ncell, _stream()), name)
         d = self._chain_factors(dev)
-        return self.from_device(h.view(1, nrows, ncell) * (d * d))[0]
+        return h.view(1, nrows, ncell) * (d * d)
 
     def hessian_vec(self, vector, weights=None):
         """Gauss-Newton Hessian times a model-shaped real ``vector``: ``jtvec({pair: weights[pair] * jvec(vector)[pair]})``,
@@ -986,7 +1001,7 @@ class ReciprocalSensitivity(Sensitivity):
                               f"{free:,} B are free" + ("; a smaller `columns_per_pass` needs less." if rows > 1 else "."))
         return torch.empty((rows, stride), dtype=dtype, device=dev)
 
-    def _block_products(self, dev, kc, block=None, data=None, weights=None):
+    def _block_products(self, dev, kc, block=None, data=None, weights=None, reuse=None):
         """The engine of ``jvec`` and ``jtvec`` (a block of one column, ``kc`` = 1) and of the three block methods,
         frequency by frequency with ONE ``_fields_of`` each. ``block``
         (device block): ``emg3d_dev_edge_weights`` per column and one ``emg3d_dev_sensitivity_dots_block`` per group of
@@ -997,7 +1012,12 @@ class ReciprocalSensitivity(Sensitivity):
         ``emg3d_dev_edges_to_cells`` per column -> the cell gradient (K, 3, n_cells) on the device. Uploads (the weights of
         all frequencies; ``keep='host'``: a frequency's stacks) and the look at the free HBM come before a frequency's
         first kernel: between its ``dots_block`` and its ``combine_block`` the host queues torch operations on (K, ns,
-        nr) and waits for nothing. ``data``: the coefficients of a frequency are uploaded before its ``combine_block``."""
+        nr) and waits for nothing. ``data``: the coefficients of a frequency are uploaded before its ``combine_block``.
+
+        ``reuse``: a dict that a caller of many passes of one shape (``gauss_newton_solve``) hands to every one of them:
+        the uploaded weights and every scratch buffer are made by the first pass, kept in it and used again by the later
+        ones (all passes run on one stream, in order), so that a pass uploads and allocates nothing of its own. The
+        kernels, their arguments and the results are those of a call without it."""
         import torch
         from emg3d_amd import _lib
         from emg3d_amd._device import _ptr, _stream
@@ -1011,16 +1031,26 @@ class ReciprocalSensitivity(Sensitivity):
         stride += stride & 1                             # rows of float64 on 16-byte boundaries
         combine = data is not None or weights is not None
         wbuf = tbufs = regridded = grad = None
+        keep = {} if reuse is None else reuse            # (a dict of this call alone: nothing outlives it)
+
+        def kept(key, make):
+            if key not in keep:
+                keep[key] = make()
+            return keep[key]
         if block is not None:
-            wbuf = self._block_scratch(kc, stride, torch.float64, dev, 'edge weights')
+            wbuf = kept('wbuf', lambda: self._block_scratch(kc, stride, torch.float64, dev, 'edge weights'))
             # the derivative chain of the mapping for the whole block: vector_k * d sigma / d property_k
             on_model = block * self._chain_factors(dev)
             regridded = {0: on_model}
-        wdevs = {}
+        wdevs = keep.get('wdevs', {})
         if combine:
-            tbufs = {}                                   # field type -> (kc, stride) edge vectors
-            grad = torch.zeros((K, 3, ncell), dtype=torch.float64, device=dev)
-            if weights is not None:
+            tbufs = kept('tbufs', dict)                  # field type -> (kc, stride) edge vectors
+            if 'grad' in keep:
+                grad = keep['grad'].zero_()
+            else:
+                grad = keep['grad'] = torch.zeros((K, 3, ncell), dtype=torch.float64, device=dev)
+            if weights is not None and 'wdevs' not in keep:
+                keep['wdevs'] = wdevs
                 # every frequency's weights go up BEFORE the first kernel (an upload from pageable memory waits for the
                 # stream): between dots_block and combine_block there are only torch operations on (K, ns, nr)
                 for fname, mine, *_ in per_freq:
@@ -1060,8 +1090,8 @@ class ReciprocalSensitivity(Sensitivity):
                 kappa = np.conj(1.0 / -smu0) * -smu0
                 scale = complex(-smu0 / kappa)
                 ws_len = L.emg3d_sensitivity_dots_block_ws_len(ns, nr, kc, n)
-                ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
-                res = torch.empty((K, ns, nr), dtype=ftype, device=dev)
+                ws = kept(('ws', fname), lambda: torch.empty(ws_len, dtype=torch.float64, device=dev))
+                res = kept(('res', fname), lambda: torch.empty((K, ns, nr), dtype=ftype, device=dev))
                 dots, name = self._entry('emg3d_dev_sensitivity_dots_block', estack)
                 for g0 in range(0, K, kc):
                     g1 = min(g0 + kc, K)
@@ -1192,6 +1222,224 @@ class ReciprocalSensitivity(Sensitivity):
         block = self._check_device_block(block, dev) if on_dev else self._upload_block(block, dev)
         out = self._gradient_block(self._block_products(dev, kc, block=block, weights=w)[1])
         return out if (on_dev if on_device is None else on_device) else self.from_device(out)
+
+    # ------------------------------------------- regulariser and the inner Gauss-Newton solve ---
+    @staticmethod
+    def _check_dampings(dampings):
+        """``dampings`` as a float64 array (K,), K >= 1; raises unless it is 1-D, real, finite and > 0."""
+        lam = np.asarray(dampings)
+        if (lam.ndim != 1 or lam.size < 1 or lam.dtype.kind not in 'fiu' or not np.all(np.isfinite(lam)) or
+                not np.all(lam > 0)):
+            raise ValueError("`dampings` must be a 1-D sequence of K >= 1 finite values > 0. "
+                             f"Provided: {lam.dtype} {lam.shape}"
+                             f"{'' if lam.size > 8 or lam.ndim != 1 else ' ' + str(lam.tolist())}.")
+        return np.ascontiguousarray(lam, dtype=np.float64)
+
+    @staticmethod
+    def _check_regulariser(smallness, smoothness):
+        """(alpha_s, alpha_x, alpha_y, alpha_z) as floats; raises unless all are finite and >= 0 and one is > 0."""
+        sm = np.asarray(smoothness)
+        if sm.shape != (3,) or sm.dtype.kind not in 'fiu' or not np.all(np.isfinite(sm)) or not np.all(sm >= 0):
+            raise ValueError("`smoothness` must be three finite values >= 0 (alpha_x, alpha_y, alpha_z). "
+                             f"Provided: {smoothness!r}.")
+        if (isinstance(smallness, bool) or not isinstance(smallness, (int, float, np.integer, np.floating)) or
+                not np.isfinite(smallness) or smallness < 0):
+            raise ValueError(f"`smallness` must be a finite value >= 0. Provided: {smallness!r}.")
+        if smallness == 0 and not sm.any():
+            raise ValueError("`smallness` and `smoothness` must not all be zero: the regulariser would be the zero "
+                             f"operator. Provided: smallness={smallness!r}, smoothness={smoothness!r}.")
+        return (float(smallness),) + tuple(float(a) for a in sm)
+
+    def _check_active(self, active):
+        """``active`` as a bool array shaped like the cells, or None."""
+        if active is None:
+            return None
+        a, shape = np.asarray(active), tuple(self.model.grid.shape_cells)
+        if a.dtype != bool or a.shape != shape:
+            raise ValueError(f"`active` must be a bool array of shape {shape}, one value per cell. "
+                             f"Provided: {a.dtype} {a.shape}.")
+        return a
+
+    @staticmethod
+    def _check_count(name, value):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+            raise ValueError(f"`{name}` must be an integer >= 1. Provided: {value!r}.")
+        return int(value)
+
+    def _check_rhs(self, rhs, K):
+        """``rhs`` of ``gauss_newton_solve``, validated without a device: (is on the device, is ONE vector for all
+        columns, the block -- NumPy (K or 1, n, nx, ny, nz) or the tensor as given)."""
+        import torch
+        n, shape, allowed = self._block_shapes()
+        ncell = self.model.grid.n_cells
+        if isinstance(rhs, torch.Tensor):
+            if rhs.ndim == 2:
+                self._check_device_block(rhs[None])
+                return True, True, rhs[None]
+            block = self._check_device_block(rhs)
+        else:
+            v = np.asarray(rhs)
+            if v.shape in allowed and not np.iscomplexobj(v):
+                return False, True, np.asarray(v, dtype=np.float64).reshape((1, n) + shape)
+            try:
+                block = self._check_vectors(rhs)
+            except ValueError as e:
+                raise ValueError(str(e).replace('`vectors`', '`rhs`')) from None
+        if len(block) != K:
+            raise ValueError(f"`rhs` must be one model-shaped vector or a block of K = len(dampings) = {K} vectors. "
+                             f"Provided: a block of {len(block)} ({n} x {ncell} cells each).")
+        return isinstance(rhs, torch.Tensor), False, block
+
+    def _regulariser_geometry(self, active, dev):
+        """(nx, ny, nz, device widths hx, hy, hz, device mask as uint8 with cells x fastest or None)."""
+        import torch
+        if self._widths is None or self._widths[0].device != dev:
+            self._widths = [torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).to(dev) for h in self.model.grid.h]
+        mask = None
+        if active is not None:
+            mask = torch.from_numpy(np.ascontiguousarray(active.ravel(order='F').astype(np.uint8))).to(dev)
+        return tuple(self.model.grid.shape_cells) + tuple(self._widths) + (mask,)
+
+    def _regulariser(self, geo, alphas, p, q, beta=0.0, lam=None, pq=None, ws=None):
+        """One ``emg3d_dev_model_regulariser`` on the device blocks ``p`` -> ``q``."""
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        nx, ny, nz, hx, hy, hz, mask = geo
+        K, n, _ = p.shape
+        mask, lam, pq, wsp = (None if t is None else _ptr(t) for t in (mask, lam, pq, ws))
+        _lib.check(_lib.lib().emg3d_dev_model_regulariser(
+            nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, mask, K * n, n, _ptr(p), _ptr(q), beta, lam, pq, wsp,
+            0 if ws is None else ws.numel(), _stream()), 'emg3d_dev_model_regulariser')
+        return q
+
+    def regulariser_vec_block(self, vectors, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None, on_device=None):
+        """The model regulariser ``R`` applied to a block of K model vectors, every component of every vector on its
+        own: the finite-volume smallness-plus-roughness operator on the model grid,
+
+            (R v)[c] = a[c] (smallness V_c v[c] + sum_d smoothness[d] sum_{faces f of c along d} a[c'] A_f / l_f (v[c] - v[c']))
+
+        with the cell volume ``V_c``, the face area ``A_f``, the distance ``l_f`` of the two cell centres and the mask
+        ``a`` = ``active`` (bool, shaped like the cells; ``None``: all cells). Faces on the boundary of the grid and
+        towards an inactive cell are left out (Neumann), rows of inactive cells are 0; ``R`` is symmetric positive
+        semi-definite and annihilates constants exactly when ``smallness`` is 0. It acts on the model's own parameters,
+        whatever the mapping.
+
+        ``vectors`` and ``on_device``: as for ``hessian_vec_block`` (a device block gives a device block). One
+        ``emg3d_dev_model_regulariser`` for the block; neither forward fields nor a solve are needed.
+        With it a user forms right-hand sides such as ``-(g + lambda R (m - m_ref))`` for ``gauss_newton_solve``."""
+        import torch
+        alphas = self._check_regulariser(smallness, smoothness)     # raises before any GPU work, as do the next two
+        mask = self._check_active(active)
+        on_dev, block = self._check_block(vectors)
+        dev = self._device()
+        block = self._check_device_block(block, dev) if on_dev else self._upload_block(block, dev)
+        out = self._regulariser(self._regulariser_geometry(mask, dev), alphas, block, torch.empty_like(block))
+        return out if (on_dev if on_device is None else on_device) else self.from_device(out)
+
+    def gauss_newton_solve(self, rhs, dampings, weights=None, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None,
+                           tol=1e-3, maxit=50, precondition=True, check_every=4, on_device=None, columns_per_pass=8):
+        """The inner linear solve of a Gauss-Newton step for K dampings at once: column ``k`` solves
+
+            (Re(J^H W J) + dampings[k] R) x_k = b_k
+
+        by preconditioned conjugate gradients, from ``x_k = 0`` until ``|r_k| <= tol |b_k|`` (``b_k`` masked by
+        ``active``; 2-norms over all components). The K iterations are independent but share every operator
+        application: ``H p`` is ONE ``hessian_vec_block`` pass over the kept fields for all columns, everything else a
+        few fused kernels on the device blocks. Returns ``(x, info)``.
+
+        rhs: one model-shaped vector, used for every column, or a block of K = ``len(dampings)`` vectors; NumPy as
+            ``jvec_block`` takes them, or on the device (a block (K, n, n_cells) of ``to_device``; one vector: (n,
+            n_cells)). ``x`` is NumPy ``(K,) +`` the shape ``jtvec`` returns, or a device block if ``rhs`` is on the
+            device; ``on_device`` True / False decides otherwise.
+        dampings: K >= 1 finite values > 0. weights: as for ``hessian_diagonal``.
+        smallness, smoothness, active: the regulariser ``R`` of ``regulariser_vec_block``. Inactive cells are taken
+            out of the system: their entries of ``x`` are exactly 0.
+        precondition: Jacobi, ``1 / (hessian_diagonal(weights) + dampings[k] diag R)``, formed inside the kernels from
+            the two diagonals, which all columns share (where that sum is not positive: 1). Needs every computational
+            grid to be the model grid, as ``hessian_diagonal`` does. False: no preconditioner.
+        check_every: the host reads the table of the per-column scalars (64 B per column) every so many iterations --
+            the only download inside the loop -- and stops when no column is running, or at ``maxit``. A column that
+            has stopped is frozen ON THE DEVICE: its ``x`` keeps its bits however long the others run, so the result
+            does not depend on ``check_every``, bit for bit; the passes after the last column has stopped are wasted.
+
+        info: ``iterations`` (K,), ``relative_residual`` (K,) ``|r_k| / |b_k|`` of the recurrence, ``state`` (K,) -- 0
+        stopped by ``maxit``, 1 converged, 2 breakdown (``<p, (H + lambda R) p> <= 0``), 3 a sum was not finite --,
+        ``history`` (list of (K,) relative residuals, one per look at the table, the one after the set-up first) and
+        ``hessian_passes``.
+
+        The weights are uploaded once and one set of scratch buffers serves all passes. ``keep='host'``: every pass
+        uploads the two stacks of every frequency again, as every block product does -- ``kept_bytes`` over PCIe per
+        iteration; ``keep='device'`` is the mode this method is meant for. No solve: ``n_solves`` does not move."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        kc = self._check_columns(columns_per_pass)              # everything is validated before any GPU work
+        lam = self._check_dampings(dampings)
+        alphas = self._check_regulariser(smallness, smoothness)
+        mask = self._check_active(active)
+        if isinstance(tol, bool) or not isinstance(tol, (float, np.floating)) or not 0 < tol < 1:
+            raise ValueError(f"`tol` must be a float in (0, 1). Provided: {tol!r}.")
+        maxit, check_every = self._check_count('maxit', maxit), self._check_count('check_every', check_every)
+        w = self._check_weights(weights)
+        K = len(lam)
+        on_dev, single, b = self._check_rhs(rhs, K)
+        if precondition:
+            self._require_model_grid('gauss_newton_solve(precondition=True)', 'before the modulus is taken')
+        dev = self._device()
+        self.forward()
+        L = _lib.lib()
+        n, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
+        b = self._check_device_block(b, dev) if on_dev else self._upload_block(b, dev)
+        r = (b.expand(K, n, ncell) if single else b).clone()    # the residual, updated in place
+        x, p = torch.zeros_like(r), torch.zeros_like(r)
+        geo = self._regulariser_geometry(mask, dev)
+        nx, ny, nz, hx, hy, hz, dmask = geo
+        hd = rd = None
+        if precondition:
+            hd = self._hessian_diagonal_block(w, dev)[0].contiguous()
+            rd = torch.empty(ncell, dtype=torch.float64, device=dev)
+            _lib.check(L.emg3d_dev_model_regulariser_diagonal(
+                nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, None if dmask is None else _ptr(dmask), _ptr(rd),
+                _stream()), 'emg3d_dev_model_regulariser_diagonal')
+        host = np.zeros((K, L.emg3d_pcg_table_len(K) // K))     # lambda, <b,b>, <r,z> new / old, <p,q>, <r,r>, iterations, state
+        host[:, 0] = lam
+        table = torch.from_numpy(host).to(dev)
+        dlam = torch.from_numpy(lam).to(dev)
+        pq = torch.zeros(K, dtype=torch.float64, device=dev)
+        ws_len = L.emg3d_pcg_ws_len(ncell, K)
+        ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+        rws = torch.empty(L.emg3d_model_regulariser_ws_len(nx, ny, nz, K * n, n), dtype=torch.float64, device=dev)
+        opt = [None if t is None else _ptr(t) for t in (hd, rd, dmask)]
+
+        def step(first, q=None):
+            _lib.check(L.emg3d_dev_pcg_update(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), None if q is None else _ptr(q),
+                                              *opt, _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_update')
+            _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, float(tol), _ptr(table), _ptr(pq), _ptr(ws), ws_len,
+                                              _stream()), 'emg3d_dev_pcg_scalar')
+            _lib.check(L.emg3d_dev_pcg_direction(ncell, n, K, first, _ptr(p), _ptr(r), *opt, _ptr(table), _stream()),
+                       'emg3d_dev_pcg_direction')
+
+        def look():
+            t = table.cpu().numpy()
+            with np.errstate(invalid='ignore', divide='ignore'):
+                rel = np.where(t[:, 1] > 0, np.sqrt(t[:, 5] / t[:, 1]), 0.0)
+            history.append(rel)
+            return t, rel
+        history, passes, reuse = [], 0, {}
+        step(1)
+        t, rel = look()
+        for it in range(1, maxit + 1):
+            if not np.any(t[:, 7] == 0):
+                break
+            q = self._gradient_block(self._block_products(dev, kc, block=p, weights=w, reuse=reuse)[1])
+            passes += 1
+            self._regulariser(geo, alphas, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws)
+            step(0, q)
+            if it % check_every == 0 or it == maxit:
+                t, rel = look()
+        info = {'iterations': t[:, 6].astype(int), 'relative_residual': rel, 'state': t[:, 7].astype(int),
+                'history': history, 'hessian_passes': passes}
+        return (x if (on_dev if on_device is None else on_device) else self.from_device(x)), info
 
     # ------------------------------------------------------- data-space normal matrix ---
     def _data_rows(self):

@@ -577,6 +577,61 @@ int emg3d_dev_sensitivity_combine_block_sp(size_t n, int is_complex, const void 
                                            const void *coef, int nv, void *t, size_t t_stride,
                                            void *stream);
 
+/* ---- the inner solve of a Gauss-Newton step: regulariser and block PCG -----------
+ * (R v)[c] = a[c] (alpha_s V_c v[c] + sum_{d} alpha_d sum_{faces f of c along d} a[c'] A_f / l_f (v[c] - v[c'])) on a
+ * tensor grid of nx x ny x nz cells, x fastest: V_c cell volume, A_f face area, l_f half the sum of the two widths
+ * along d, a = mask (device, one byte per cell, 0 / 1; NULL: all active). Faces on the boundary and towards an
+ * inactive cell are left out, rows of inactive cells are 0. hx / hy / hz: device cell widths. The coefficients are
+ * formed in the kernel from the widths, once per cell for all vectors, and never stored (csrc/regularise.h).
+ *
+ * emg3d_dev_model_regulariser: q[j] = beta q[j] + lam[j / vec_per_col] (R p[j]) for j < nvec; vector j starts
+ * j * nx ny nz doubles behind vector 0 (the device blocks of the block products with vec_per_col components per
+ * column); nvec a multiple of vec_per_col; beta = 0: q is written, not read; lam: device, nvec / vec_per_col
+ * doubles, NULL: 1; p and q must not overlap. pq not NULL: pq[col] = sum over the column's vec_per_col vectors of
+ * <p, q_new> (device, written), from the same pass. No floating-point atomics: every wave of 64 cells (a row piece
+ * of the (64, 4, 1) workgroup) adds its share with shuffles and writes one partial sum, ws[col * nwaves + wave]
+ * with wave = 4 * (bx + nbx (by + nby iz)) + row piece; a second launch adds the partials of a column, thread t of
+ * 256 taking t, t + 256, ... in ascending order, then a binary tree over the threads. The order depends on the sizes
+ * alone: the same call gives the same bits. ws: at least emg3d_model_regulariser_ws_len doubles (0: bad sizes),
+ * needed only with pq. A direction may have 1 or 2 cells. nx ny nz < 2^31. */
+size_t emg3d_model_regulariser_ws_len(int nx, int ny, int nz, int nvec, int vec_per_col);
+int emg3d_dev_model_regulariser(int nx, int ny, int nz, const double *hx, const double *hy, const double *hz,
+                                double alpha_s, double alpha_x, double alpha_y, double alpha_z,
+                                const unsigned char *mask, int nvec, int vec_per_col, const double *p, double *q,
+                                double beta, const double *lam, double *pq, double *ws, size_t ws_len,
+                                void *stream);
+/* diag[c] = (R)_cc: a[c] (alpha_s V_c + sum of the coefficients of the faces that R keeps); nx ny nz doubles. */
+int emg3d_dev_model_regulariser_diagonal(int nx, int ny, int nz, const double *hx, const double *hy,
+                                         const double *hz, double alpha_s, double alpha_x, double alpha_y,
+                                         double alpha_z, const unsigned char *mask, double *diag, void *stream);
+/* Block preconditioned CG: ncol independent systems whose vectors are the columns (vec_per_col x n_cells doubles
+ * each, contiguous) of x, r, p, q. The scalars live in `table` (device), 8 doubles per column:
+ *   [0] lambda  [1] <b,b>  [2] <r,z>  [3] <r,z> before  [4] <p,q>  [5] <r,r>  [6] iterations  [7] state
+ * state 0 running, 1 converged (<r,r> <= tol^2 <b,b>), 2 breakdown (<p,q> <= 0, or <r,z> <= 0 with r != 0), 3 a sum is not finite. The host
+ * writes lambda and zeros; a column whose state is not 0 is FROZEN: no kernel below touches its x, r, p again.
+ * Preconditioner z = M r: r / (hdiag + lambda rdiag) (hdiag: vec_per_col x n_cells, shared by the columns; rdiag:
+ * n_cells; both device; where the sum is not > 0: r), r itself with hdiag NULL, and 0 where mask is 0.
+ *
+ * emg3d_dev_pcg_update, per running column: alpha = <r,z> / pq[col], x += alpha p, r -= alpha q (0 where mask is 0),
+ * and the partial sums of <r, z> and <r, r> with the new r into ws (per workgroup; at least emg3d_pcg_ws_len
+ * doubles). pq[col] not in (0, inf]: the column is left as it is. first != 0: the set-up, r (holding b) is masked
+ * and summed, x / p / q / pq are not used.
+ * emg3d_dev_pcg_scalar: one workgroup adds the partial sums of emg3d_dev_pcg_update in a fixed order (thread t of
+ * 256: t, t + 256, ..., then a binary tree) and advances the table: pq[col] <= 0 or NaN -> state 2 / 3; otherwise
+ * <r,z> -> [3], the sums -> [2], [5], iterations + 1, and the new state. first != 0: [1] = [5] = <b,b>, state 1 if
+ * that is 0.
+ * emg3d_dev_pcg_direction, per running column: p = z + ([2] / [3]) p with z = M r formed again from r (first: p = z). */
+size_t emg3d_pcg_table_len(int ncol);
+size_t emg3d_pcg_ws_len(size_t n_cells, int ncol);
+int emg3d_dev_pcg_update(size_t n_cells, int vec_per_col, int ncol, int first, double *x, double *r, const double *p,
+                         const double *q, const double *hdiag, const double *rdiag, const unsigned char *mask,
+                         const double *table, const double *pq, double *ws, size_t ws_len, void *stream);
+int emg3d_dev_pcg_scalar(size_t n_cells, int ncol, int first, double tol, double *table, const double *pq,
+                         const double *ws, size_t ws_len, void *stream);
+int emg3d_dev_pcg_direction(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *r,
+                            const double *hdiag, const double *rdiag, const unsigned char *mask,
+                            const double *table, void *stream);
+
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid
  * (emg3d/models.py:322-366). values (nx,ny,nz) -> out (mx,my,mz), doubles, x fastest. Per axis

@@ -22,14 +22,21 @@ and ``'single'`` -- the two block kernels alone against K launches of the single
 TB/s on the bytes the stacks hold plus the w / t rows), then ``hessian_vec_block`` on a device block, result left on the
 device, against K calls of ``hessian_vec`` on NumPy vectors, with ``keep='device'`` and ``keep='host'``. Writes
 profiles/block_products_times.txt.
+Leg ``gnsolve``: one iteration of the block PCG of ``ReciprocalSensitivity.gauss_newton_solve``, K = 1, 4,
+8 dampings, for ``field_dtype='double'`` and ``'single'``: the new kernels alone (HIP events) with their rates on
+algorithmic bytes beside a device copy that moves the same bytes, then 10 iterations split by events into the Hessian pass
+and every new kernel, and the same 10 iterations written with torch operations around ``hessian_vec_block`` and a slicing
+regulariser -- what a user can write without the method --, the two taking turns for five rounds. Writes
+profiles/gauss_newton_solve_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
-                                     [--leg all|products|hessian|gram|single|block] [--field-dtype double|single]
+                                     [--leg all|products|hessian|gram|single|block|gnsolve] [--field-dtype double|single]
                                      [--out profiles/sensitivity_times.txt]
                                      [--hessian-out profiles/hessian_diagonal_times.txt]
                                      [--gram-out profiles/data_gram_times.txt]
                                      [--single-out profiles/reciprocal_single_times.txt]
                                      [--block-out profiles/block_products_times.txt]
+                                     [--gnsolve-out profiles/gauss_newton_solve_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -542,18 +549,207 @@ def block_methods(rec, say, repeat, label):
         del H, R, B
 
 
+GN_K = (1, 4, 8)
+GN_ITERATIONS, GN_ROUNDS, GN_CHECK = 10, 5, 4
+GN_REG = (1e-6, 1.0, 1.0, 1.0)              # smallness, smoothness x / y / z
+
+
+def gnsolve_block(rec, say, launches):
+    """One iteration of the block PCG two ways on the kept fields of ``rec``: with the kernels of csrc/regularise.h in
+    the order ``gauss_newton_solve`` launches them, and with torch operations around ``hessian_vec_block``."""
+    from emg3d_amd import _lib
+    from emg3d_amd._device import _ptr, _stream
+    L = _lib.lib()
+    grid = rec.model.grid
+    n, ncell = gradient._NCOMP[rec.model.case], grid.n_cells
+    nx, ny, nz = grid.shape_cells
+    dev = torch.device('cuda', torch.cuda.current_device())
+    w = rec._check_weights(None)
+    geo = rec._regulariser_geometry(None, dev)
+    hx, hy, hz = geo[3:6]
+    hd = rec._hessian_diagonal_block(w, dev)[0].contiguous()
+    rd = torch.empty(ncell, dtype=torch.float64, device=dev)
+    _lib.check(L.emg3d_dev_model_regulariser_diagonal(nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *GN_REG, None, _ptr(rd),
+                                                      _stream()), 'emg3d_dev_model_regulariser_diagonal')
+    lam0 = float(hd.mean() / rd.mean())
+    # the slicing regulariser of the torch route: its coefficients are made once, as a user would
+    shape = (nz, ny, nx)
+    hs = [h.view(v) for h, v in zip((hx, hy, hz), ((1, 1, nx), (1, ny, 1), (nz, 1, 1)))]
+    vol = hs[0] * hs[1] * hs[2]
+    faces = []
+    for d, (dim, h) in enumerate(zip((-1, -2, -3), (hx, hy, hz))):
+        area = (hs[1] * hs[2], hs[0] * hs[2], hs[0] * hs[1])[d]
+        dist = (0.5 * (h[:-1] + h[1:])).view([len(h) - 1 if k == 3 + dim else 1 for k in range(3)])
+        faces.append((dim, GN_REG[1 + d] * area / dist))
+
+    def torch_R(v):
+        v = v.view((v.shape[0], n) + shape)
+        out = GN_REG[0] * vol * v
+        for dim, coef in faces:
+            m = v.shape[dim]
+            d = coef * (v.narrow(dim, 0, m - 1) - v.narrow(dim, 1, m - 1))
+            out.narrow(dim, 0, m - 1).add_(d)
+            out.narrow(dim, 1, m - 1).sub_(d)
+        return out.view(v.shape[0], n, ncell)
+
+    def timed(fn, count):
+        """Median and fastest of ``count`` launches (ms, HIP events), after two warm-up launches."""
+        ms = []
+        for i in range(count + 2):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= 2:
+                ms.append(a.elapsed_time(b))
+        return float(np.median(ms)), float(min(ms))
+    rng = np.random.default_rng(2)
+    for K in GN_K:
+        lam = lam0 * 10.0 ** np.linspace(-1, 1, K)
+        b = rec.to_device(rng.standard_normal((K, n) + tuple(grid.shape_cells)))
+        host = np.zeros((K, 8))
+        host[:, 0] = lam
+        dlam = torch.from_numpy(lam).to(dev)
+        pq = torch.zeros(K, dtype=torch.float64, device=dev)
+        ws_len = L.emg3d_pcg_ws_len(ncell, K)
+        ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+        rws = torch.empty(L.emg3d_model_regulariser_ws_len(nx, ny, nz, K * n, n), dtype=torch.float64, device=dev)
+        x, r, p, q = (torch.zeros_like(b) for _ in range(4))
+        table = torch.zeros((K, 8), dtype=torch.float64, device=dev)
+        reuse = {}
+
+        def k_reg():
+            rec._regulariser(geo, GN_REG, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws)
+
+        def k_update(first=0):
+            _lib.check(L.emg3d_dev_pcg_update(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), _ptr(q), _ptr(hd), _ptr(rd), None,
+                                              _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_update')
+
+        def k_scalar(first=0):
+            _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, 1e-30, _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()),
+                       'emg3d_dev_pcg_scalar')
+
+        def k_direction(first=0):
+            _lib.check(L.emg3d_dev_pcg_direction(ncell, n, K, first, _ptr(p), _ptr(r), _ptr(hd), _ptr(rd), None, _ptr(table),
+                                                 _stream()), 'emg3d_dev_pcg_direction')
+
+        def k_hessian():
+            nonlocal q
+            q = rec._gradient_block(rec._block_products(dev, 8, block=p, weights=w, reuse=reuse)[1])
+
+        def start():
+            table.copy_(torch.from_numpy(host))
+            x.zero_()
+            r.copy_(b)
+            k_update(1), k_scalar(1), k_direction(1)
+
+        def fused(parts=None):
+            """GN_ITERATIONS iterations as gauss_newton_solve runs them; ``parts``: event times per piece are added."""
+            start()
+            for it in range(1, GN_ITERATIONS + 1):
+                for name, fn in (('hessian pass', k_hessian), ('regulariser', k_reg), ('update', k_update),
+                                 ('scalar step', k_scalar), ('direction', k_direction)):
+                    if parts is None:
+                        fn()
+                    else:
+                        a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        fn()
+                        e.record()
+                        parts.setdefault(name, []).append((a, e))
+                if it % GN_CHECK == 0 or it == GN_ITERATIONS:
+                    state = table.cpu().numpy()
+            return x, state[:, 5] / state[:, 1]
+
+        tl = torch.from_numpy(lam).to(dev).view(K, 1, 1)
+
+        def composed():
+            """The same iterations from torch operations: what a user writes around hessian_vec_block."""
+            xt, rt = torch.zeros_like(b), b.clone()
+            m = 1.0 / (hd + tl * rd)
+            z = rt * m
+            pt = z.clone()
+            rz = (rt * z).sum((1, 2))
+            bb = (rt * rt).sum((1, 2))
+            for it in range(1, GN_ITERATIONS + 1):
+                qt = rec.hessian_vec_block(pt) + tl * torch_R(pt)
+                alpha = (rz / (pt * qt).sum((1, 2))).view(K, 1, 1)
+                xt += alpha * pt
+                rt -= alpha * qt
+                z = rt * m
+                new = (rt * z).sum((1, 2))
+                rr = (rt * rt).sum((1, 2))
+                pt = z + (new / rz).view(K, 1, 1) * pt
+                rz = new
+                if it % GN_CHECK == 0 or it == GN_ITERATIONS:
+                    rel = (rr / bb).cpu().numpy()
+            return xt, rel
+
+        def wall(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / GN_ITERATIONS, out
+        # the kernels alone on a running state (one iteration in, so that p and q hold what an iteration gives them)
+        start(), k_hessian(), k_reg()
+        elems = K * n * ncell
+        shared = (n + 1) * ncell * 8
+        for name, fn, nbytes in (('regulariser', k_reg, elems * 24), ('update', k_update, elems * 48 + shared),
+                                 ('direction', k_direction, elems * 24 + shared)):
+            src = torch.empty(nbytes // 16, dtype=torch.float64, device=dev)
+            dst = torch.empty_like(src)
+            med, best = timed(fn, launches)
+            cmed, cbest = timed(lambda: dst.copy_(src), launches)
+            say(f"  K = {K}: {name:12s} median {med:7.3f} ms (fastest {best:7.3f}), {nbytes / 1e6:8.1f} MB algorithmic = "
+                f"{nbytes / med / 1e9:5.2f} TB/s; copy that moves the same bytes {cmed:7.3f} ms (fastest {cbest:7.3f}) = "
+                f"{nbytes / cmed / 1e9:5.2f} TB/s; ratio to the copy rate {cmed / med:4.2f}")
+            del src, dst
+        med, best = timed(k_scalar, launches)
+        say(f"  K = {K}: scalar step  median {med:7.3f} ms (fastest {best:7.3f}), one workgroup")
+        # ten iterations, the two routes taking turns
+        fused(), composed()                                  # warm-up
+        tf, tc = [], []
+        for _ in range(GN_ROUNDS):
+            t, (xf, relf) = wall(fused)
+            tf.append(t)
+            t, (xc, relc) = wall(composed)
+            tc.append(t)
+        diff = float((xf - xc).abs().max() / xc.abs().max())
+        parts = {}
+        fused(parts)
+        torch.cuda.synchronize()
+        split = ", ".join(f"{name} {np.mean([a.elapsed_time(e) for a, e in ev]):.3f}" for name, ev in parts.items())
+        say(f"  K = {K}: per iteration (wall, synchronised, {GN_ITERATIONS} iterations, table read every {GN_CHECK}), rounds: "
+            f"new kernels {' '.join(f'{t:.3f}' for t in tf)} ms (mean {np.mean(tf):.3f}, spread {max(tf) - min(tf):.3f}); torch "
+            f"operations {' '.join(f'{t:.3f}' for t in tc)} ms (mean {np.mean(tc):.3f}, spread {max(tc) - min(tc):.3f}); ratio "
+            f"of the means {np.mean(tc) / np.mean(tf):.2f}; max-norm relative difference of x {diff:.1e}; |r|^2 / |b|^2 after "
+            f"{GN_ITERATIONS}: {relf.max():.2e} / {relc.max():.2e}")
+        say(f"  K = {K}: split of an iteration (HIP events, mean, ms): {split}")
+        t0 = time.perf_counter()
+        _, info = rec.gauss_newton_solve(b, lam, smallness=GN_REG[0], smoothness=GN_REG[1:], tol=1e-30, maxit=GN_ITERATIONS,
+                                        check_every=GN_CHECK)
+        torch.cuda.synchronize()
+        say(f"  K = {K}: gauss_newton_solve(maxit={GN_ITERATIONS}) with its set-up (hessian_diagonal, diag R, table): "
+            f"{1e3 * (time.perf_counter() - t0):.1f} ms, {info['hessian_passes']} passes, states {info['state'].tolist()}")
+        del b, x, r, p, q, reuse
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
-    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block'), default='all',
+    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block', 'gnsolve'), default='all',
                     help="products: the inner iteration four ways and its two reductions; hessian: hessian_diagonal against "
                          "the row-by-row route (needs only the set-up of ReciprocalSensitivity); gram: data_gram against the "
                          "route through jtvec, one frequency and two (the same set-up, once per survey); single: "
                          "field_dtype 'double' and 'single' side by side (not part of 'all'); block: K vectors per pass, the "
-                         "block kernels and hessian_vec_block against K single calls (not part of 'all')")
+                         "block kernels and hessian_vec_block against K single calls (not part of 'all'); gnsolve: an "
+                         "iteration of gauss_newton_solve, its kernels and the same iteration from torch operations (not "
+                         "part of 'all')")
     ap.add_argument('--field-dtype', choices=('double', 'single'), default='double',
                     help="how ReciprocalSensitivity keeps its fields in the reciprocal, hessian and gram legs")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
@@ -561,6 +757,7 @@ def main():
     ap.add_argument('--gram-out', default=os.path.join(ROOT, 'profiles', 'data_gram_times.txt'))
     ap.add_argument('--single-out', default=os.path.join(ROOT, 'profiles', 'reciprocal_single_times.txt'))
     ap.add_argument('--block-out', default=os.path.join(ROOT, 'profiles', 'block_products_times.txt'))
+    ap.add_argument('--gnsolve-out', default=os.path.join(ROOT, 'profiles', 'gauss_newton_solve_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -655,6 +852,21 @@ def main():
             del host
         os.makedirs(os.path.dirname(os.path.abspath(args.block_out)), exist_ok=True)
         with open(args.block_out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
+    if args.leg == 'gnsolve':
+        lines[1] = (f"# {wl['label']}; {K} sources x 1 frequency, {len(recs)} receivers; (H + lambda_k R) x_k = b_k, K dampings over "
+                    f"two decades, Jacobi, smallness {GN_REG[0]}, smoothness {GN_REG[1:]}, all weights one; times in ms")
+        for name in ('double', 'single'):
+            rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6),
+                                                 keep='device', batch=K, field_dtype=name)
+            rec.forward()
+            say(f"field_dtype='{name}': {rec!r}")
+            gnsolve_block(rec, say, args.launches)
+            rec.release()
+            del rec
+        os.makedirs(os.path.dirname(os.path.abspath(args.gnsolve_out)), exist_ok=True)
+        with open(args.gnsolve_out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
         return
     if args.leg in ('hessian', 'gram'):
