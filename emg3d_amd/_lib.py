@@ -132,6 +132,14 @@ SIGNATURES = {
     'emg3d_dev_model_regulariser': (_ci, [_ci] * 3 + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp, _ci, _ci, _vp, _vp,
                                           ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
     'emg3d_dev_model_regulariser_diagonal': (_ci, [_ci] * 3 + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp, _vp, _vp]),
+    # the weighted / sparse-norm (IRLS) regulariser and the per-component diagonal of the preconditioner
+    'emg3d_dev_model_regulariser_weighted': (_ci, [_ci] * 3 + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp, _vp, _sz, _vp, _sz] +
+                                                   [ctypes.c_double] * 6 + [_ci, _ci, _vp, _vp, ctypes.c_double, _vp, _vp,
+                                                                            _vp, _sz, _vp]),
+    'emg3d_dev_model_regulariser_weighted_diagonal': (_ci, [_ci] * 3 + [_vp] * 3 + [ctypes.c_double] * 4 +
+                                                      [_vp, _vp, _sz, _vp, _sz] + [ctypes.c_double] * 6 + [_ci, _vp, _vp]),
+    'emg3d_dev_pcg_update_rd': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 6 + [_sz] + [_vp] * 4 + [_sz, _vp]),
+    'emg3d_dev_pcg_direction_rd': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 4 + [_sz] + [_vp] * 3),
     'emg3d_pcg_table_len': (_sz, [_ci]),
     'emg3d_pcg_ws_len': (_sz, [_sz, _ci]),
     'emg3d_dev_pcg_update': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 10 + [_sz, _vp]),

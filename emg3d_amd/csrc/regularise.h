@@ -23,12 +23,16 @@
 //   k_regulariser_finish      one workgroup per column: thread t adds the partials t, t + 256, ... in ascending order,
 //                             then a binary tree over the 256 threads in LDS.
 //   k_model_regulariser_diagonal   diag R from the same coefficients.
+//   k_model_regulariser_weighted, k_model_regulariser_weighted_diagonal   the same two for the weighted / sparse-norm
+//                             (IRLS) form of R (described where they stand): the coefficients carry
+//                             cell weights and powers of the linearisation vector's values and gradients, per component.
 //   k_pcg_update              grid (blocks, K). Column k, if its state is 0: alpha = <r,z> / <p,q>, x += alpha p,
 //                             r -= alpha q (0 on inactive cells), z = M r with the Jacobi preconditioner M formed here
 //                             from the two shared diagonals and the column's lambda, and the workgroup's share of
 //                             <r, z> and <r, r> with the NEW r: ws[(k * blocks + block) * 2 + {0, 1}]. z is not stored
 //                             (k_pcg_direction forms it again from r: 16 / K B per element for the diagonals instead of
 //                             8 B written and 8 B read). A column whose state is not 0 is not touched at all.
+//                             rdiag_stride: doubles between the diagonals of R of two components (0: one for all).
 //   k_pcg_scalar              ONE workgroup: adds the partial sums (thread t takes t, t + 256, ..., then the LDS tree),
 //                             advances the table and freezes a column whose state leaves 0.
 //   k_pcg_direction           p = z + beta p, beta = <r,z> / <r,z>_old (first: p = z), columns of state 0 only.
@@ -153,6 +157,142 @@ __global__ __launch_bounds__(256) void k_model_regulariser_diagonal(RegGeo G, do
     diag[c] = act ? d : 0.0;
 }
 
+// ---- the weighted / sparse-norm (IRLS) operator ----
+// Component k of a column has cell weights w_k >= 0 and linearisation values u_k, both shared by all columns:
+//
+//     cs[c]   = alpha_s V_c        w[c]               rho(p_s, eps_s; u[c])
+//     cf[c,f] = (coefficient of reg_coefs) (w[c] + w[c']) / 2  rho(p_d, eps_g; (u[c] - u[c']) / l_f)
+//     rho(p, eps; t) = (t^2 + eps^2)^(p / 2 - 1), and 1 -- nothing read, nothing multiplied -- for p = 2.
+//
+// Every factor of a face comes out the same from either side (w[c] + w[c'] commutes, t enters as fma(t, t, eps^2) and
+// (-t)(-t) = t t), and the factors are multiplied in one order: R stays symmetric as stored and >= 0.
+struct RegW {
+    const double *w, *u;        // NULL: weights 1; no linearisation (all norms 2)
+    size_t wstride, ustride;    // doubles between the components' rows; 0: one row for all
+    double ps, px, py, pz;      // the norms of the smallness term and of the three directions
+    double es2, eg2;            // eps_s^2, eps_g^2
+};
+
+// rho(p, .; t) for p != 2, x2 = t^2 + eps^2 > 0: p = 1 and p = 0 without the power function
+__device__ __forceinline__ double reg_rho(double p, double x2)
+{
+    if (p == 1.0) return 1.0 / sqrt(x2);
+    if (p == 0.0) return 1.0 / x2;
+    return pow(x2, 0.5 * p - 1.0);
+}
+
+// reg_coefs for component k with the weights and the norms worked in. A face whose coefficient is 0 has off[f] = 0:
+// its w and u are those of the cell itself, nothing of an inactive cell or past the grid is read.
+// es = w[c] rho(p_s, eps_s; u[c]), the factor that cs carries on top of alpha_s V_c (exactly 1 without weights and with
+// p_s = 2).
+__device__ __forceinline__ bool reg_coefs_weighted(const RegGeo &G, const RegW &W, int k, int ix, int iy, int iz, size_t c,
+                                                   double &cs, double &es, double (&cf)[6], int (&off)[6])
+{
+    const bool act = reg_coefs(G, ix, iy, iz, c, cs, cf, off);
+    const double *w = W.w ? W.w + (size_t)k * W.wstride + c : nullptr;
+    const double *u = W.u ? W.u + (size_t)k * W.ustride + c : nullptr;
+    es = 1.0;
+    if (w) {
+        const double wc = w[0];
+        es = wc;
+#pragma unroll
+        for (int f = 0; f < 6; ++f) cf[f] *= 0.5 * (wc + w[off[f]]);
+    }
+    if (W.ps != 2.0) es *= reg_rho(W.ps, fma(u[0], u[0], W.es2));
+    cs *= es;
+    const double pd[3] = {W.px, W.py, W.pz};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        if (pd[d] == 2.0) continue;
+        const double hc = d == 0 ? G.hx[ix] : d == 1 ? G.hy[iy] : G.hz[iz];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int f = 2 * d + s;
+            const int j = (d == 0 ? ix : d == 1 ? iy : iz) + (off[f] == 0 ? 0 : s ? 1 : -1);
+            const double hn = d == 0 ? G.hx[j] : d == 1 ? G.hy[j] : G.hz[j];
+            const double t = (u[0] - u[off[f]]) / (0.5 * (hn + hc));
+            cf[f] *= reg_rho(pd[d], fma(t, t, W.eg2));
+        }
+    }
+    return act;
+}
+
+// k_model_regulariser with the coefficients of all VPC components formed up front in registers (VPC x 7 doubles), then
+// the same column-outer / component-inner loop: the same seven additions in the same order, the same partial sums.
+// With weights of 1 and norms of 2 the bits must be those of k_model_regulariser, and which products the compiler fuses
+// into which sums differs from kernel to kernel (here: beta q + l r came out as fma(beta, q, l r), there as fma(l, r,
+// beta q)). So contraction is off in this kernel and the loop spells out the operations that k_model_regulariser
+// compiles to: cf[0] (v - p0), then cs v fused onto it, then the faces 1 .. 5 fused on one after the other; beta q,
+// then l r fused onto it; v q_new fused onto the wave's sum. test_weighted_regulariser.py holds the two to each other.
+template <int VPC>
+__global__ __launch_bounds__(256) void k_model_regulariser_weighted(RegGeo G, RegW W, int ncol, const double *__restrict__ p,
+                                                                    double *__restrict__ q, double beta,
+                                                                    const double *__restrict__ lam, double *ws)
+{
+#pragma clang fp contract(off)
+    const int ix = blockIdx.x * 64 + threadIdx.x, iy = blockIdx.y * 4 + threadIdx.y, iz = blockIdx.z;
+    const bool inside = ix < G.nx && iy < G.ny;
+    const size_t ncell = (size_t)G.nx * G.ny * G.nz;
+    const size_t c = inside ? (size_t)ix + (size_t)G.nx * ((size_t)iy + (size_t)G.ny * iz) : 0;
+    double cs[VPC], cf[VPC][6];
+    int off[6] = {0, 0, 0, 0, 0, 0};
+    bool act = false;
+#pragma unroll
+    for (int k = 0; k < VPC; ++k) {
+        cs[k] = 0.0;
+#pragma unroll
+        for (int f = 0; f < 6; ++f) cf[k][f] = 0.0;
+        double es;
+        if (inside) act = reg_coefs_weighted(G, W, k, ix, iy, iz, c, cs[k], es, cf[k], off);
+    }
+    const size_t nwaves = (size_t)gridDim.x * gridDim.y * gridDim.z * 4;
+    const size_t wave = ((size_t)blockIdx.x + (size_t)gridDim.x * ((size_t)blockIdx.y + (size_t)gridDim.y * blockIdx.z)) * 4 +
+                        threadIdx.y;
+    for (int col = 0; col < ncol; ++col) {
+        const double l = lam ? lam[col] : 1.0;
+        double acc = 0.0;
+        if (inside) {
+#pragma unroll
+            for (int k = 0; k < VPC; ++k) {
+                const size_t base = ((size_t)col * VPC + k) * ncell + c;
+                const double *pc = p + base;
+                const double v = pc[0];
+                double r = fma(cs[k], v, cf[k][0] * (v - pc[off[0]]));
+#pragma unroll
+                for (int f = 1; f < 6; ++f) r = fma(cf[k][f], v - pc[off[f]], r);
+                r = act ? r : 0.0;
+                const double qn = beta != 0.0 ? fma(l, r, beta * q[base]) : l * r;
+                q[base] = qn;
+                acc = fma(v, qn, acc);
+            }
+        }
+        if (ws) {
+            acc = wave_sum(acc);
+            if (threadIdx.x == 0) ws[(size_t)col * nwaves + wave] = acc;
+        }
+    }
+}
+
+// diag[k * ncell + c] = (R_k)_cc, k < vpc. As above, spelled out: k_model_regulariser_diagonal compiles its first sum
+// to fma(alpha_s, V_c, cf[0]), so here it is fma(alpha_s, V_c es, cf[0]) -- the same bits when es is exactly 1.
+__global__ __launch_bounds__(256) void k_model_regulariser_weighted_diagonal(RegGeo G, RegW W, int vpc, double *diag)
+{
+#pragma clang fp contract(off)
+    const int ix = blockIdx.x * 64 + threadIdx.x, iy = blockIdx.y * 4 + threadIdx.y, iz = blockIdx.z;
+    if (ix >= G.nx || iy >= G.ny) return;
+    const size_t ncell = (size_t)G.nx * G.ny * G.nz;
+    const size_t c = (size_t)ix + (size_t)G.nx * ((size_t)iy + (size_t)G.ny * iz);
+    for (int k = 0; k < vpc; ++k) {
+        double cs, es, cf[6];
+        int off[6];
+        const bool act = reg_coefs_weighted(G, W, k, ix, iy, iz, c, cs, es, cf, off);
+        double d = fma(G.as, G.hx[ix] * G.hy[iy] * G.hz[iz] * es, cf[0]);
+#pragma unroll
+        for (int f = 1; f < 6; ++f) d += cf[f];
+        diag[(size_t)k * ncell + c] = act ? d : 0.0;
+    }
+}
+
 // z = M r for one element: Jacobi 1 / (hdiag + lambda rdiag) (hdiag: of the element, rdiag: of its cell), the identity
 // without diagonals or where the sum is not positive; 0 on inactive cells
 __device__ __forceinline__ double pcg_precondition(double r, bool act, bool jacobi, double hd, double rd, double lam)
@@ -168,8 +308,8 @@ __device__ __forceinline__ bool pcg_pq_ok(double pq) { return pq > 0.0 && pq <= 
 __global__ __launch_bounds__(PCG_BLOCK) void k_pcg_update(size_t ncell, int vpc, int first, double *x, double *r,
                                                           const double *__restrict__ p, const double *__restrict__ q,
                                                           const double *__restrict__ hdiag, const double *__restrict__ rdiag,
-                                                          const unsigned char *__restrict__ mask, const double *table,
-                                                          const double *pq, double *ws)
+                                                          size_t rdiag_stride, const unsigned char *__restrict__ mask,
+                                                          const double *table, const double *pq, double *ws)
 {
     const int col = blockIdx.y;
     const double *row = table + (size_t)col * PCG_ROW;
@@ -179,7 +319,7 @@ __global__ __launch_bounds__(PCG_BLOCK) void k_pcg_update(size_t ncell, int vpc,
     double arz = 0.0, arr = 0.0;
     if (run) {
         for (int k = 0; k < vpc; ++k) {
-            const size_t comp = (size_t)k * ncell, base = ((size_t)col * vpc + k) * ncell;
+            const size_t comp = (size_t)k * ncell, rcomp = (size_t)k * rdiag_stride, base = ((size_t)col * vpc + k) * ncell;
             for (size_t c = (size_t)blockIdx.x * PCG_BLOCK + threadIdx.x; c < ncell; c += (size_t)gridDim.x * PCG_BLOCK) {
                 const bool act = !mask || mask[c];
                 double rn = r[base + c];
@@ -190,7 +330,7 @@ __global__ __launch_bounds__(PCG_BLOCK) void k_pcg_update(size_t ncell, int vpc,
                 rn = act ? rn : 0.0;
                 r[base + c] = rn;
                 const double z = pcg_precondition(rn, act, hdiag != nullptr, hdiag ? hdiag[comp + c] : 0.0,
-                                                  hdiag ? rdiag[c] : 0.0, lam);
+                                                  hdiag ? rdiag[rcomp + c] : 0.0, lam);
                 arz += rn * z;
                 arr += rn * rn;
             }
@@ -249,7 +389,7 @@ __global__ __launch_bounds__(PCG_BLOCK) void k_pcg_scalar(int ncol, int nblocks,
 
 __global__ __launch_bounds__(PCG_BLOCK) void k_pcg_direction(size_t ncell, int vpc, int first, double *p,
                                                              const double *__restrict__ r, const double *__restrict__ hdiag,
-                                                             const double *__restrict__ rdiag,
+                                                             const double *__restrict__ rdiag, size_t rdiag_stride,
                                                              const unsigned char *__restrict__ mask, const double *table)
 {
     const int col = blockIdx.y;
@@ -258,11 +398,11 @@ __global__ __launch_bounds__(PCG_BLOCK) void k_pcg_direction(size_t ncell, int v
     const double lam = row[PCG_LAM];
     const double beta = first ? 0.0 : row[PCG_RZ] / row[PCG_RZ_OLD];
     for (int k = 0; k < vpc; ++k) {
-        const size_t comp = (size_t)k * ncell, base = ((size_t)col * vpc + k) * ncell;
+        const size_t comp = (size_t)k * ncell, rcomp = (size_t)k * rdiag_stride, base = ((size_t)col * vpc + k) * ncell;
         for (size_t c = (size_t)blockIdx.x * PCG_BLOCK + threadIdx.x; c < ncell; c += (size_t)gridDim.x * PCG_BLOCK) {
             const bool act = !mask || mask[c];
             const double z = pcg_precondition(r[base + c], act, hdiag != nullptr, hdiag ? hdiag[comp + c] : 0.0,
-                                              hdiag ? rdiag[c] : 0.0, lam);
+                                              hdiag ? rdiag[rcomp + c] : 0.0, lam);
             p[base + c] = first ? z : z + beta * p[base + c];
         }
     }
@@ -278,6 +418,28 @@ inline bool reg_sizes_ok(int nx, int ny, int nz)
     return nx >= 1 && ny >= 1 && nz >= 1 && (long long)nx * ny * nz < (1LL << 31) && nz <= 65535 && (ny + 3) / 4 <= 65535;
 }
 inline size_t reg_waves(int nx, int ny, int nz) { return (size_t)((nx + 63) / 64) * ((ny + 3) / 4) * nz * 4; }
+
+// The weights, the linearisation and the norms of the weighted entries: 0 and W filled, or the error
+inline int reg_weighted_args(const char *who, size_t ncell, const double *cell_weights, size_t weights_stride,
+                             const double *linearise_at, size_t linearise_stride, double p_s, double p_x, double p_y, double p_z,
+                             double eps_s, double eps_g, RegW &W)
+{
+    const double ps[4] = {p_s, p_x, p_y, p_z};
+    bool sparse = false;
+    for (double e : ps) {
+        if (!(e >= 0.0 && e <= 2.0)) return fail(EMG3D_ERR_BADARG, (std::string(who) + ": a norm is not in [0, 2]").c_str());
+        sparse = sparse || e != 2.0;
+    }
+    if (sparse && !linearise_at)
+        return fail(EMG3D_ERR_BADARG, (std::string(who) + ": a norm other than 2 needs linearise_at").c_str());
+    if (sparse && !(eps_s > 0.0 && eps_s <= 1.7976931348623157e308 && eps_g > 0.0 && eps_g <= 1.7976931348623157e308))
+        return fail(EMG3D_ERR_BADARG, (std::string(who) + ": a norm other than 2 needs finite thresholds eps_s, eps_g > 0").c_str());
+    if ((weights_stride != 0 && weights_stride < ncell) || (linearise_stride != 0 && linearise_stride < ncell))
+        return fail(EMG3D_ERR_BADARG, (std::string(who) + ": a stride is neither 0 nor >= nx ny nz").c_str());
+    W = {cell_weights, sparse ? linearise_at : nullptr, weights_stride, linearise_stride, p_s, p_x, p_y, p_z,
+         sparse ? eps_s * eps_s : 0.0, sparse ? eps_g * eps_g : 0.0};
+    return 0;
+}
 
 }  // namespace
 
@@ -324,6 +486,61 @@ int emg3d_dev_model_regulariser_diagonal(int nx, int ny, int nz, const double *h
     return 0;
 }
 
+int emg3d_dev_model_regulariser_weighted(int nx, int ny, int nz, const double *hx, const double *hy, const double *hz,
+                                         double alpha_s, double alpha_x, double alpha_y, double alpha_z,
+                                         const unsigned char *mask, const double *cell_weights, size_t weights_stride,
+                                         const double *linearise_at, size_t linearise_stride, double p_s, double p_x,
+                                         double p_y, double p_z, double eps_s, double eps_g, int nvec, int vec_per_col,
+                                         const double *p, double *q, double beta, const double *lam, double *pq, double *ws,
+                                         size_t ws_len, void *stream)
+{
+    if (!reg_sizes_ok(nx, ny, nz) || !hx || !hy || !hz || nvec < 1 || vec_per_col < 1 || vec_per_col > 3 ||
+        nvec % vec_per_col != 0 || !p || !q || p == q || nvec / vec_per_col > 65535)
+        return fail(EMG3D_ERR_BADARG, "model_regulariser_weighted: bad argument");
+    RegW W;
+    if (int err = reg_weighted_args("model_regulariser_weighted", (size_t)nx * ny * nz, cell_weights, weights_stride,
+                                    linearise_at, linearise_stride, p_s, p_x, p_y, p_z, eps_s, eps_g, W))
+        return err;
+    if (pq && (!ws || ws_len < emg3d_model_regulariser_ws_len(nx, ny, nz, nvec, vec_per_col)))
+        return fail(EMG3D_ERR_SCRATCH, "model_regulariser_weighted: workspace too small (emg3d_model_regulariser_ws_len)");
+    const RegGeo G = {nx, ny, nz, hx, hy, hz, alpha_s, alpha_x, alpha_y, alpha_z, mask};
+    const int ncol = nvec / vec_per_col;
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((nx + 63) / 64, (ny + 3) / 4, nz), block(64, 4, 1);
+    double *wsp = pq ? ws : (double *)nullptr;
+    if (vec_per_col == 1)
+        hipLaunchKernelGGL(k_model_regulariser_weighted<1>, grid, block, 0, st, G, W, ncol, p, q, beta, lam, wsp);
+    else if (vec_per_col == 2)
+        hipLaunchKernelGGL(k_model_regulariser_weighted<2>, grid, block, 0, st, G, W, ncol, p, q, beta, lam, wsp);
+    else
+        hipLaunchKernelGGL(k_model_regulariser_weighted<3>, grid, block, 0, st, G, W, ncol, p, q, beta, lam, wsp);
+    if (pq)
+        hipLaunchKernelGGL(k_regulariser_finish, dim3(ncol), dim3(PCG_BLOCK), 0, st, (const double *)ws, reg_waves(nx, ny, nz),
+                           pq);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int emg3d_dev_model_regulariser_weighted_diagonal(int nx, int ny, int nz, const double *hx, const double *hy,
+                                                  const double *hz, double alpha_s, double alpha_x, double alpha_y,
+                                                  double alpha_z, const unsigned char *mask, const double *cell_weights,
+                                                  size_t weights_stride, const double *linearise_at, size_t linearise_stride,
+                                                  double p_s, double p_x, double p_y, double p_z, double eps_s, double eps_g,
+                                                  int vec_per_col, double *diag, void *stream)
+{
+    if (!reg_sizes_ok(nx, ny, nz) || !hx || !hy || !hz || !diag || vec_per_col < 1 || vec_per_col > 3)
+        return fail(EMG3D_ERR_BADARG, "model_regulariser_weighted_diagonal: bad argument");
+    RegW W;
+    if (int err = reg_weighted_args("model_regulariser_weighted_diagonal", (size_t)nx * ny * nz, cell_weights, weights_stride,
+                                    linearise_at, linearise_stride, p_s, p_x, p_y, p_z, eps_s, eps_g, W))
+        return err;
+    const RegGeo G = {nx, ny, nz, hx, hy, hz, alpha_s, alpha_x, alpha_y, alpha_z, mask};
+    hipLaunchKernelGGL(k_model_regulariser_weighted_diagonal, dim3((nx + 63) / 64, (ny + 3) / 4, nz), dim3(64, 4, 1), 0,
+                       (hipStream_t)stream, G, W, vec_per_col, diag);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 size_t emg3d_pcg_table_len(int ncol) { return ncol < 1 ? 0 : (size_t)ncol * PCG_ROW; }
 
 size_t emg3d_pcg_ws_len(size_t n_cells, int ncol)
@@ -332,19 +549,28 @@ size_t emg3d_pcg_ws_len(size_t n_cells, int ncol)
     return (size_t)ncol * pcg_blocks(n_cells) * 2;
 }
 
-int emg3d_dev_pcg_update(size_t n_cells, int vec_per_col, int ncol, int first, double *x, double *r, const double *p,
-                         const double *q, const double *hdiag, const double *rdiag, const unsigned char *mask,
-                         const double *table, const double *pq, double *ws, size_t ws_len, void *stream)
+int emg3d_dev_pcg_update_rd(size_t n_cells, int vec_per_col, int ncol, int first, double *x, double *r, const double *p,
+                            const double *q, const double *hdiag, const double *rdiag, size_t rdiag_stride,
+                            const unsigned char *mask, const double *table, const double *pq, double *ws, size_t ws_len,
+                            void *stream)
 {
     if (n_cells < 1 || vec_per_col < 1 || ncol < 1 || ncol > 65535 || !r || !table || !ws || (hdiag && !rdiag) ||
-        (!first && (!x || !p || !q || !pq)))
+        (rdiag_stride != 0 && rdiag_stride < n_cells) || (!first && (!x || !p || !q || !pq)))
         return fail(EMG3D_ERR_BADARG, "pcg_update: bad argument");
     if (ws_len < emg3d_pcg_ws_len(n_cells, ncol))
         return fail(EMG3D_ERR_SCRATCH, "pcg_update: workspace too small (emg3d_pcg_ws_len)");
     hipLaunchKernelGGL(k_pcg_update, dim3(pcg_blocks(n_cells), ncol), dim3(PCG_BLOCK), 0, (hipStream_t)stream, n_cells,
-                       vec_per_col, first ? 1 : 0, x, r, p, q, hdiag, rdiag, mask, table, pq, ws);
+                       vec_per_col, first ? 1 : 0, x, r, p, q, hdiag, rdiag, rdiag_stride, mask, table, pq, ws);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int emg3d_dev_pcg_update(size_t n_cells, int vec_per_col, int ncol, int first, double *x, double *r, const double *p,
+                         const double *q, const double *hdiag, const double *rdiag, const unsigned char *mask,
+                         const double *table, const double *pq, double *ws, size_t ws_len, void *stream)
+{
+    return emg3d_dev_pcg_update_rd(n_cells, vec_per_col, ncol, first, x, r, p, q, hdiag, rdiag, 0, mask, table, pq, ws, ws_len,
+                                   stream);
 }
 
 int emg3d_dev_pcg_scalar(size_t n_cells, int ncol, int first, double tol, double *table, const double *pq, const double *ws,
@@ -360,16 +586,24 @@ int emg3d_dev_pcg_scalar(size_t n_cells, int ncol, int first, double tol, double
     return 0;
 }
 
+int emg3d_dev_pcg_direction_rd(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *r,
+                               const double *hdiag, const double *rdiag, size_t rdiag_stride, const unsigned char *mask,
+                               const double *table, void *stream)
+{
+    if (n_cells < 1 || vec_per_col < 1 || ncol < 1 || ncol > 65535 || !p || !r || !table || (hdiag && !rdiag) ||
+        (rdiag_stride != 0 && rdiag_stride < n_cells))
+        return fail(EMG3D_ERR_BADARG, "pcg_direction: bad argument");
+    hipLaunchKernelGGL(k_pcg_direction, dim3(pcg_blocks(n_cells), ncol), dim3(PCG_BLOCK), 0, (hipStream_t)stream, n_cells,
+                       vec_per_col, first ? 1 : 0, p, r, hdiag, rdiag, rdiag_stride, mask, table);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int emg3d_dev_pcg_direction(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *r,
                             const double *hdiag, const double *rdiag, const unsigned char *mask, const double *table,
                             void *stream)
 {
-    if (n_cells < 1 || vec_per_col < 1 || ncol < 1 || ncol > 65535 || !p || !r || !table || (hdiag && !rdiag))
-        return fail(EMG3D_ERR_BADARG, "pcg_direction: bad argument");
-    hipLaunchKernelGGL(k_pcg_direction, dim3(pcg_blocks(n_cells), ncol), dim3(PCG_BLOCK), 0, (hipStream_t)stream, n_cells,
-                       vec_per_col, first ? 1 : 0, p, r, hdiag, rdiag, mask, table);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return emg3d_dev_pcg_direction_rd(n_cells, vec_per_col, ncol, first, p, r, hdiag, rdiag, 0, mask, table, stream);
 }
 
 }  // extern "C"

@@ -1260,6 +1260,93 @@ class ReciprocalSensitivity(Sensitivity):
                              f"Provided: {a.dtype} {a.shape}.")
         return a
 
+    def _check_irls(self, cell_weights, norms, linearise_at, irls_eps):
+        """The weighted / sparse-norm arguments of the regulariser, validated without a device. None if all four are
+        None; otherwise (weights, norms, u, eps): weights NumPy (1 or n, n_cells) with cells x fastest, a tensor as given
+        or None; norms four floats; u NumPy (n, n_cells), a tensor as given or None; eps two floats (0 without u)."""
+        import torch
+        if cell_weights is None and norms is None and linearise_at is None and irls_eps is None:
+            return None
+        n, shape, allowed = self._block_shapes()
+        ncell = self.model.grid.n_cells
+
+        def rows(a):
+            return np.stack([c.ravel(order='F') for c in a.reshape((-1,) + shape)])
+
+        def tensor_ok(t, shapes):
+            return t.dtype == torch.float64 and tuple(t.shape) in shapes and t.is_contiguous() and t.device.type == 'cuda'
+        w = cell_weights
+        if isinstance(w, torch.Tensor):
+            if not tensor_ok(w, [(ncell,), (n, ncell)]):
+                raise ValueError(f"`cell_weights` on the device must be a contiguous float64 tensor of shape ({ncell},) or "
+                                 f"({n}, {ncell}). Provided: {w.dtype} {tuple(w.shape)} on {w.device}, contiguous: "
+                                 f"{w.is_contiguous()}.")
+        elif w is not None:
+            a = np.asarray(w)
+            if (a.dtype.kind not in 'fiu' or a.shape not in (shape, (n,) + shape) or not np.all(np.isfinite(a)) or
+                    not np.all(a >= 0)):
+                raise ValueError(f"`cell_weights` must be real, finite and >= 0 with shape {shape} (one array for all "
+                                 f"components) or {(n,) + shape}. Provided: {a.dtype} {a.shape}.")
+            w = rows(np.asarray(a, dtype=np.float64))
+        ps = (2.0, 2.0, 2.0, 2.0)
+        if norms is not None:
+            a = np.asarray(norms)
+            if a.shape != (4,) or a.dtype.kind not in 'fiu' or not np.all(np.isfinite(a)) or not np.all((a >= 0) & (a <= 2)):
+                raise ValueError("`norms` must be four finite values in [0, 2] (p_s, p_x, p_y, p_z). "
+                                 f"Provided: {norms!r}.")
+            ps = tuple(float(p) for p in a)
+        sparse = any(p != 2.0 for p in ps)
+        u, eps = linearise_at, (0.0, 0.0)
+        if not sparse and (u is not None or irls_eps is not None):
+            raise ValueError("`linearise_at` and `irls_eps` belong to norms other than 2: with all four norms 2 they would "
+                             f"be ignored. Provided: norms={norms!r}, linearise_at "
+                             f"{'given' if u is not None else 'None'}, irls_eps={irls_eps!r}.")
+        if sparse:
+            if u is None or irls_eps is None:
+                raise ValueError("a norm other than 2 needs `linearise_at` (the deviation m - m_ref at which the weights "
+                                 f"are frozen) and `irls_eps`. Provided: norms={norms!r}, linearise_at "
+                                 f"{'given' if u is not None else 'None'}, irls_eps={irls_eps!r}.")
+            if isinstance(u, torch.Tensor):
+                if not tensor_ok(u, [(n, ncell)]):
+                    raise ValueError(f"`linearise_at` on the device must be a contiguous float64 tensor of shape ({n}, "
+                                     f"{ncell}). Provided: {u.dtype} {tuple(u.shape)} on {u.device}, contiguous: "
+                                     f"{u.is_contiguous()}.")
+            else:
+                a = np.asarray(u)
+                if a.dtype.kind not in 'fiu' or a.shape not in allowed or not np.all(np.isfinite(a)):
+                    raise ValueError("`linearise_at` must be one real, finite model-shaped vector of shape "
+                                     f"{' or '.join(str(s) for s in allowed[::-1])}. Provided: {a.dtype} {a.shape}.")
+                u = rows(np.asarray(a, dtype=np.float64))
+            a = np.asarray(irls_eps)
+            if a.shape != (2,) or a.dtype.kind not in 'fiu' or not np.all(np.isfinite(a)) or not np.all(a > 0):
+                raise ValueError("`irls_eps` must be two finite values > 0 (eps_s, eps_g). "
+                                 f"Provided: {irls_eps!r}.")
+            eps = tuple(float(e) for e in a)
+        return w, ps, u, eps
+
+    def _upload_irls(self, irls, dev):
+        """The result of ``_check_irls`` with its arrays in HBM (uploads come before kernels), or None."""
+        import torch
+        if irls is None:
+            return None
+
+        def up(a, name):
+            if a is None or not isinstance(a, torch.Tensor):
+                return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            if a.device != dev:
+                raise ValueError(f"`{name}` must be on the device of the fields ({dev}). Provided: on {a.device}.")
+            return a
+        w, ps, u, eps = irls
+        return up(w, 'cell_weights'), ps, up(u, 'linearise_at'), eps
+
+    @staticmethod
+    def _irls_args(irls, ncell):
+        """The C arguments between ``mask`` and ``nvec`` of the weighted entries."""
+        from emg3d_amd._device import _ptr
+        w, ps, u, eps = irls
+        wstride = ncell if w is not None and w.ndim == 2 and w.shape[0] > 1 else 0
+        return (None if w is None else _ptr(w), wstride, None if u is None else _ptr(u), 0 if u is None else ncell) + ps + eps
+
     @staticmethod
     def _check_count(name, value):
         if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
@@ -1300,19 +1387,27 @@ class ReciprocalSensitivity(Sensitivity):
             mask = torch.from_numpy(np.ascontiguousarray(active.ravel(order='F').astype(np.uint8))).to(dev)
         return tuple(self.model.grid.shape_cells) + tuple(self._widths) + (mask,)
 
-    def _regulariser(self, geo, alphas, p, q, beta=0.0, lam=None, pq=None, ws=None):
-        """One ``emg3d_dev_model_regulariser`` on the device blocks ``p`` -> ``q``."""
+    def _regulariser(self, geo, alphas, p, q, beta=0.0, lam=None, pq=None, ws=None, irls=None):
+        """One ``emg3d_dev_model_regulariser`` on the device blocks ``p`` -> ``q``; with ``irls`` (of ``_upload_irls``)
+        one ``emg3d_dev_model_regulariser_weighted``."""
         from emg3d_amd import _lib
         from emg3d_amd._device import _ptr, _stream
         nx, ny, nz, hx, hy, hz, mask = geo
-        K, n, _ = p.shape
+        K, n, ncell = p.shape
         mask, lam, pq, wsp = (None if t is None else _ptr(t) for t in (mask, lam, pq, ws))
+        if irls is not None:
+            _lib.check(_lib.lib().emg3d_dev_model_regulariser_weighted(
+                nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, mask, *self._irls_args(irls, ncell), K * n, n, _ptr(p),
+                _ptr(q), beta, lam, pq, wsp, 0 if ws is None else ws.numel(), _stream()),
+                'emg3d_dev_model_regulariser_weighted')
+            return q
         _lib.check(_lib.lib().emg3d_dev_model_regulariser(
             nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, mask, K * n, n, _ptr(p), _ptr(q), beta, lam, pq, wsp,
             0 if ws is None else ws.numel(), _stream()), 'emg3d_dev_model_regulariser')
         return q
 
-    def regulariser_vec_block(self, vectors, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None, on_device=None):
+    def regulariser_vec_block(self, vectors, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None, on_device=None, *,
+                              cell_weights=None, norms=None, linearise_at=None, irls_eps=None):
         """The model regulariser ``R`` applied to a block of K model vectors, every component of every vector on its
         own: the finite-volume smallness-plus-roughness operator on the model grid,
 
@@ -1326,18 +1421,44 @@ class ReciprocalSensitivity(Sensitivity):
 
         ``vectors`` and ``on_device``: as for ``hessian_vec_block`` (a device block gives a device block). One
         ``emg3d_dev_model_regulariser`` for the block; neither forward fields nor a solve are needed.
-        With it a user forms right-hand sides such as ``-(g + lambda R (m - m_ref))`` for ``gauss_newton_solve``."""
+        With it a user forms right-hand sides such as ``-(g + lambda R (m - m_ref))`` for ``gauss_newton_solve``.
+
+        The weighted / sparse-norm form (keyword only, all ``None``: the operator above through the same entry point
+        as ever; otherwise ``emg3d_dev_model_regulariser_weighted``). Component ``k`` of a vector has
+        cell weights ``w_k`` and linearisation values ``u_k``, the same for all K vectors:
+
+            (R v)[c] = a[c] (cs[c] v[c] + sum_f cf[c,f] (v[c] - v[c']))
+            cs[c]    = smallness V_c w[c] rho(p_s, eps_s; u[c])
+            cf[c,f]  = smoothness[d] a[c'] (A_f / l_f) (w[c] + w[c']) / 2 rho(p_d, eps_g; (u[c] - u[c']) / l_f)
+            rho(p, eps; t) = (t^2 + eps^2)^(p / 2 - 1), exactly 1 for p = 2
+
+        cell_weights: real, finite, >= 0, shaped like the cells (one array for all components) or like a model vector
+            ``(n, nx, ny, nz)`` -- depth or sensitivity weighting, for example a power of ``hessian_diagonal()``; or a
+            float64 device tensor ``(n_cells,)`` / ``(n, n_cells)``, cells x fastest. ``None``: 1.
+        norms: ``(p_s, p_x, p_y, p_z)`` in [0, 2], the measures of the deviation and of its three gradients in their
+            lagged-diffusivity (IRLS, Ekblom) form. ``None``: all 2.
+        linearise_at: one model-shaped real vector (NumPy, or a device tensor ``(n, n_cells)``): the deviation
+            ``m - m_ref`` of the model's own parameters at which the weights ``rho`` are frozen. Needed exactly when a
+            norm is not 2; given with all norms 2 it raises, so that nothing is silently ignored.
+        irls_eps: ``(eps_s, eps_g)``, both > 0; needed exactly when a norm is not 2.
+
+        ``R`` stays symmetric (as stored, bit for bit) positive semi-definite and annihilates constants when
+        ``smallness`` is 0. The outer IRLS loop is the user's: it updates ``linearise_at``, cools ``irls_eps`` and
+        handles the reference model; one call is one frozen linearisation."""
         import torch
-        alphas = self._check_regulariser(smallness, smoothness)     # raises before any GPU work, as do the next two
+        alphas = self._check_regulariser(smallness, smoothness)     # raises before any GPU work, as do the next three
         mask = self._check_active(active)
+        irls = self._check_irls(cell_weights, norms, linearise_at, irls_eps)
         on_dev, block = self._check_block(vectors)
         dev = self._device()
         block = self._check_device_block(block, dev) if on_dev else self._upload_block(block, dev)
-        out = self._regulariser(self._regulariser_geometry(mask, dev), alphas, block, torch.empty_like(block))
+        irls = self._upload_irls(irls, dev)
+        out = self._regulariser(self._regulariser_geometry(mask, dev), alphas, block, torch.empty_like(block), irls=irls)
         return out if (on_dev if on_device is None else on_device) else self.from_device(out)
 
     def gauss_newton_solve(self, rhs, dampings, weights=None, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None,
-                           tol=1e-3, maxit=50, precondition=True, check_every=4, on_device=None, columns_per_pass=8):
+                           tol=1e-3, maxit=50, precondition=True, check_every=4, on_device=None, columns_per_pass=8, *,
+                           cell_weights=None, norms=None, linearise_at=None, irls_eps=None):
         """The inner linear solve of a Gauss-Newton step for K dampings at once: column ``k`` solves
 
             (Re(J^H W J) + dampings[k] R) x_k = b_k
@@ -1354,6 +1475,13 @@ class ReciprocalSensitivity(Sensitivity):
         dampings: K >= 1 finite values > 0. weights: as for ``hessian_diagonal``.
         smallness, smoothness, active: the regulariser ``R`` of ``regulariser_vec_block``. Inactive cells are taken
             out of the system: their entries of ``x`` are exactly 0.
+        cell_weights, norms, linearise_at, irls_eps (keyword only): the weighted / sparse-norm form of ``R``, as for
+            ``regulariser_vec_block``: ``R`` becomes the seven-point operator whose coefficients carry the cell weights
+            and the IRLS weights ``(t^2 + eps^2)^(p / 2 - 1)`` frozen at ``linearise_at``. They are
+            uploaded once, before the first kernel; the Jacobi preconditioner then takes the diagonal of ``R`` per
+            component. All ``None``: the entry points and the bits of the plain operator. The outer IRLS loop --
+            updating ``linearise_at``, cooling ``irls_eps``, the reference model -- is the user's, as is the rest of
+            the inversion.
         precondition: Jacobi, ``1 / (hessian_diagonal(weights) + dampings[k] diag R)``, formed inside the kernels from
             the two diagonals, which all columns share (where that sum is not positive: 1). Needs every computational
             grid to be the model grid, as ``hessian_diagonal`` does. False: no preconditioner.
@@ -1377,6 +1505,7 @@ class ReciprocalSensitivity(Sensitivity):
         lam = self._check_dampings(dampings)
         alphas = self._check_regulariser(smallness, smoothness)
         mask = self._check_active(active)
+        irls = self._check_irls(cell_weights, norms, linearise_at, irls_eps)
         if isinstance(tol, bool) or not isinstance(tol, (float, np.floating)) or not 0 < tol < 1:
             raise ValueError(f"`tol` must be a float in (0, 1). Provided: {tol!r}.")
         maxit, check_every = self._check_count('maxit', maxit), self._check_count('check_every', check_every)
@@ -1390,6 +1519,7 @@ class ReciprocalSensitivity(Sensitivity):
         L = _lib.lib()
         n, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
         b = self._check_device_block(b, dev) if on_dev else self._upload_block(b, dev)
+        irls = self._upload_irls(irls, dev)
         r = (b.expand(K, n, ncell) if single else b).clone()    # the residual, updated in place
         x, p = torch.zeros_like(r), torch.zeros_like(r)
         geo = self._regulariser_geometry(mask, dev)
@@ -1397,10 +1527,16 @@ class ReciprocalSensitivity(Sensitivity):
         hd = rd = None
         if precondition:
             hd = self._hessian_diagonal_block(w, dev)[0].contiguous()
-            rd = torch.empty(ncell, dtype=torch.float64, device=dev)
-            _lib.check(L.emg3d_dev_model_regulariser_diagonal(
-                nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, None if dmask is None else _ptr(dmask), _ptr(rd),
-                _stream()), 'emg3d_dev_model_regulariser_diagonal')
+            if irls is None:
+                rd = torch.empty(ncell, dtype=torch.float64, device=dev)
+                _lib.check(L.emg3d_dev_model_regulariser_diagonal(
+                    nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, None if dmask is None else _ptr(dmask), _ptr(rd),
+                    _stream()), 'emg3d_dev_model_regulariser_diagonal')
+            else:                                                   # one diagonal of R per component
+                rd = torch.empty((n, ncell), dtype=torch.float64, device=dev)
+                _lib.check(L.emg3d_dev_model_regulariser_weighted_diagonal(
+                    nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, None if dmask is None else _ptr(dmask),
+                    *self._irls_args(irls, ncell), n, _ptr(rd), _stream()), 'emg3d_dev_model_regulariser_weighted_diagonal')
         host = np.zeros((K, L.emg3d_pcg_table_len(K) // K))     # lambda, <b,b>, <r,z> new / old, <p,q>, <r,r>, iterations, state
         host[:, 0] = lam
         table = torch.from_numpy(host).to(dev)
@@ -1411,7 +1547,18 @@ class ReciprocalSensitivity(Sensitivity):
         rws = torch.empty(L.emg3d_model_regulariser_ws_len(nx, ny, nz, K * n, n), dtype=torch.float64, device=dev)
         opt = [None if t is None else _ptr(t) for t in (hd, rd, dmask)]
 
+        def step_rd(first, q=None):
+            _lib.check(L.emg3d_dev_pcg_update_rd(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), None if q is None else _ptr(q),
+                                                 opt[0], opt[1], ncell, opt[2], _ptr(table), _ptr(pq), _ptr(ws), ws_len,
+                                                 _stream()), 'emg3d_dev_pcg_update_rd')
+            _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, float(tol), _ptr(table), _ptr(pq), _ptr(ws), ws_len,
+                                              _stream()), 'emg3d_dev_pcg_scalar')
+            _lib.check(L.emg3d_dev_pcg_direction_rd(ncell, n, K, first, _ptr(p), _ptr(r), opt[0], opt[1], ncell, opt[2],
+                                                    _ptr(table), _stream()), 'emg3d_dev_pcg_direction_rd')
+
         def step(first, q=None):
+            if irls is not None:
+                return step_rd(first, q)
             _lib.check(L.emg3d_dev_pcg_update(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), None if q is None else _ptr(q),
                                               *opt, _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_update')
             _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, float(tol), _ptr(table), _ptr(pq), _ptr(ws), ws_len,
@@ -1433,7 +1580,7 @@ class ReciprocalSensitivity(Sensitivity):
                 break
             q = self._gradient_block(self._block_products(dev, kc, block=p, weights=w, reuse=reuse)[1])
             passes += 1
-            self._regulariser(geo, alphas, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws)
+            self._regulariser(geo, alphas, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws, irls=irls)
             step(0, q)
             if it % check_every == 0 or it == maxit:
                 t, rel = look()

@@ -604,6 +604,41 @@ int emg3d_dev_model_regulariser(int nx, int ny, int nz, const double *hx, const 
 int emg3d_dev_model_regulariser_diagonal(int nx, int ny, int nz, const double *hx, const double *hy,
                                          const double *hz, double alpha_s, double alpha_x, double alpha_y,
                                          double alpha_z, const unsigned char *mask, double *diag, void *stream);
+/* The weighted / sparse-norm (IRLS, lagged diffusivity) form of R. Component k < vec_per_col <= 3 of
+ * a column has cell weights w_k >= 0 and linearisation values u_k, both shared by all columns:
+ *   cs[c]   = alpha_s V_c w[c] rho(p_s, eps_s; u[c])
+ *   cf[c,f] = alpha_d a[c'] (A_f / l_f) (w[c] + w[c']) / 2 rho(p_d, eps_g; (u[c] - u[c']) / l_f)
+ *   rho(p, eps; t) = (t^2 + eps^2)^(p / 2 - 1), exactly 1 (nothing read, nothing multiplied) for p = 2
+ * in (R v)[c] = a[c] (cs[c] v[c] + sum_f cf[c,f] (v[c] - v[c'])); everything else as emg3d_dev_model_regulariser. Each
+ * factor of a face is the same from either side: R is symmetric as stored, positive semi-definite, and annihilates
+ * constants when alpha_s = 0. cell_weights: device, row k starts k * weights_stride doubles behind row 0 (stride 0: one
+ * row of nx ny nz doubles for all components), NULL: 1. linearise_at: device, rows as for the weights by
+ * linearise_stride; NULL only if all four norms are 2 (then it and the thresholds are not used). The norms p_s, p_x,
+ * p_y, p_z lie in [0, 2]; p = 1 takes a reciprocal square root, p = 0 a reciprocal, every other the power function.
+ * The coefficients of all components are formed in registers once per cell (w and u of the neighbours through the
+ * cache, a face that R leaves out reads the cell itself) and serve all columns; then the loop, the order of the
+ * additions, the partial sums of <p, q_new> in ws and the second launch are those of emg3d_dev_model_regulariser
+ * (ws: emg3d_model_regulariser_ws_len). With cell_weights NULL or all 1.0 and all norms 2 the bits are those of
+ * emg3d_dev_model_regulariser. EMG3D_ERR_BADARG, nothing launched: vec_per_col > 3, nvec not a multiple of it, a norm
+ * outside [0, 2] or not finite, a norm != 2 with linearise_at NULL or with eps_s or eps_g not finite and > 0, a stride
+ * that is neither 0 nor >= nx ny nz, and what emg3d_dev_model_regulariser refuses. */
+int emg3d_dev_model_regulariser_weighted(int nx, int ny, int nz, const double *hx, const double *hy, const double *hz,
+                                         double alpha_s, double alpha_x, double alpha_y, double alpha_z,
+                                         const unsigned char *mask, const double *cell_weights, size_t weights_stride,
+                                         const double *linearise_at, size_t linearise_stride, double p_s, double p_x,
+                                         double p_y, double p_z, double eps_s, double eps_g, int nvec, int vec_per_col,
+                                         const double *p, double *q, double beta, const double *lam, double *pq,
+                                         double *ws, size_t ws_len, void *stream);
+/* diag[k * nx ny nz + c] = (R_k)_cc of the weighted operator of component k < vec_per_col: vec_per_col x nx ny nz
+ * doubles, 0 on inactive cells. With weights NULL or 1.0 and all norms 2: the bits of
+ * emg3d_dev_model_regulariser_diagonal in every row. */
+int emg3d_dev_model_regulariser_weighted_diagonal(int nx, int ny, int nz, const double *hx, const double *hy,
+                                                  const double *hz, double alpha_s, double alpha_x, double alpha_y,
+                                                  double alpha_z, const unsigned char *mask, const double *cell_weights,
+                                                  size_t weights_stride, const double *linearise_at,
+                                                  size_t linearise_stride, double p_s, double p_x, double p_y,
+                                                  double p_z, double eps_s, double eps_g, int vec_per_col, double *diag,
+                                                  void *stream);
 /* Block preconditioned CG: ncol independent systems whose vectors are the columns (vec_per_col x n_cells doubles
  * each, contiguous) of x, r, p, q. The scalars live in `table` (device), 8 doubles per column:
  *   [0] lambda  [1] <b,b>  [2] <r,z>  [3] <r,z> before  [4] <p,q>  [5] <r,r>  [6] iterations  [7] state
@@ -631,6 +666,17 @@ int emg3d_dev_pcg_scalar(size_t n_cells, int ncol, int first, double tol, double
 int emg3d_dev_pcg_direction(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *r,
                             const double *hdiag, const double *rdiag, const unsigned char *mask,
                             const double *table, void *stream);
+/* emg3d_dev_pcg_update / emg3d_dev_pcg_direction with one diagonal of R per component: component k reads
+ * rdiag[k * rdiag_stride + c]. rdiag_stride 0: one row for all components (the two entries above, which forward
+ * here with 0: the same kernels, the same bits); otherwise >= n_cells and rdiag holds vec_per_col rows
+ * (emg3d_dev_model_regulariser_weighted_diagonal). It changes only an address. */
+int emg3d_dev_pcg_update_rd(size_t n_cells, int vec_per_col, int ncol, int first, double *x, double *r, const double *p,
+                            const double *q, const double *hdiag, const double *rdiag, size_t rdiag_stride,
+                            const unsigned char *mask, const double *table, const double *pq, double *ws,
+                            size_t ws_len, void *stream);
+int emg3d_dev_pcg_direction_rd(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *r,
+                               const double *hdiag, const double *rdiag, size_t rdiag_stride,
+                               const unsigned char *mask, const double *table, void *stream);
 
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid

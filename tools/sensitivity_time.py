@@ -27,7 +27,9 @@ Leg ``gnsolve``: one iteration of the block PCG of ``ReciprocalSensitivity.gauss
 algorithmic bytes beside a device copy that moves the same bytes, then 10 iterations split by events into the Hessian pass
 and every new kernel, and the same 10 iterations written with torch operations around ``hessian_vec_block`` and a slicing
 regulariser -- what a user can write without the method --, the two taking turns for five rounds. Writes
-profiles/gauss_newton_solve_times.txt.
+profiles/gauss_newton_solve_times.txt. Then, for 'double', the weighted / sparse-norm regulariser: its
+kernel with weights only, norms of 1 and general norms beside the plain kernel and a copy of its bytes, and an iteration of
+``gauss_newton_solve`` weighted against plain. Writes profiles/weighted_regulariser_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
                                      [--leg all|products|hessian|gram|single|block|gnsolve] [--field-dtype double|single]
@@ -37,6 +39,7 @@ profiles/gauss_newton_solve_times.txt.
                                      [--single-out profiles/reciprocal_single_times.txt]
                                      [--block-out profiles/block_products_times.txt]
                                      [--gnsolve-out profiles/gauss_newton_solve_times.txt]
+                                     [--weighted-out profiles/weighted_regulariser_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -736,6 +739,85 @@ def gnsolve_block(rec, say, launches):
         del b, x, r, p, q, reuse
 
 
+GN_NORMS = (('weights only', (2.0, 2.0, 2.0, 2.0)), ('norms 1', (1.0, 1.0, 1.0, 1.0)), ('norms general', (0.5, 1.5, 1.2, 0.7)))
+GN_EPS = (1e-2, 1e-4)
+
+
+def weighted_block(rec, say, launches):
+    """The weighted / sparse-norm regulariser on the model grid of ``rec``: its kernel with weights
+    only, with norms of 1 and with general norms beside the plain kernel of the same build and beside a copy of its
+    bytes; then an iteration of ``gauss_newton_solve``, weighted against plain, as the difference of runs of 2 x and
+    1 x ``GN_ITERATIONS`` iterations (the set-up drops out), the two taking turns."""
+    from emg3d_amd import _lib
+    L = _lib.lib()
+    grid = rec.model.grid
+    n, ncell = gradient._NCOMP[rec.model.case], grid.n_cells
+    nx, ny, nz = grid.shape_cells
+    dev = torch.device('cuda', torch.cuda.current_device())
+    geo = rec._regulariser_geometry(None, dev)
+    rng = np.random.default_rng(4)
+    wd = torch.from_numpy(rng.uniform(0.2, 5.0, (n, ncell))).to(dev)
+    ud = torch.from_numpy(rng.standard_normal((n, ncell))).to(dev)
+
+    def timed(fn, count):
+        ms = []
+        for i in range(count + 2):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= 2:
+                ms.append(a.elapsed_time(b))
+        return float(np.median(ms)), float(min(ms))
+    hd = rec._hessian_diagonal_block(rec._check_weights(None), dev)[0]
+    lam0 = float(hd.mean()) / (GN_REG[1] * float(np.mean(grid.h[0])))
+    for K in GN_K:
+        lam = lam0 * 10.0 ** np.linspace(-1, 1, K)
+        dlam = torch.from_numpy(lam).to(dev)
+        b = rec.to_device(rng.standard_normal((K, n) + tuple(grid.shape_cells)))
+        p, q = b.clone(), torch.zeros_like(b)
+        pq = torch.zeros(K, dtype=torch.float64, device=dev)
+        rws = torch.empty(L.emg3d_model_regulariser_ws_len(nx, ny, nz, K * n, n), dtype=torch.float64, device=dev)
+        elems = K * n * ncell
+        plain = timed(lambda: rec._regulariser(geo, GN_REG, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws), launches)
+        say(f"  K = {K}: plain kernel       median {plain[0]:7.3f} ms (fastest {plain[1]:7.3f}), {elems * 24 / 1e6:8.1f} MB algorithmic")
+        for name, norms in GN_NORMS:
+            sparse = any(e != 2.0 for e in norms)
+            irls = (wd, norms, ud if sparse else None, GN_EPS if sparse else (0.0, 0.0))
+            nbytes = elems * 24 + (2 if sparse else 1) * n * ncell * 8
+            med, best = timed(lambda: rec._regulariser(geo, GN_REG, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws, irls=irls),
+                              launches)
+            src = torch.empty(nbytes // 16, dtype=torch.float64, device=dev)
+            dst = torch.empty_like(src)
+            cmed, cbest = timed(lambda: dst.copy_(src), launches)
+            del src, dst
+            say(f"  K = {K}: {name:18s} median {med:7.3f} ms (fastest {best:7.3f}), {nbytes / 1e6:8.1f} MB algorithmic = "
+                f"{nbytes / med / 1e9:5.2f} TB/s; copy that moves the same bytes {cmed:7.3f} ms (fastest {cbest:7.3f}); ratio "
+                f"to the copy rate {cmed / med:4.2f}; to the plain kernel {med / plain[0]:4.2f} x, + {1e3 * (med - plain[0]):.0f} us")
+        kw = dict(smallness=GN_REG[0], smoothness=GN_REG[1:], tol=1e-30, check_every=GN_CHECK)
+        routes = (('plain', {}), ('weighted, norms 1', dict(cell_weights=wd, norms=GN_NORMS[1][1], linearise_at=ud,
+                                                           irls_eps=GN_EPS)))
+
+        def run(extra, its):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rec.gauss_newton_solve(b, lam, maxit=its, **kw, **extra)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0)
+        for _, extra in routes:
+            run(extra, GN_ITERATIONS)                          # warm-up
+        per = {name: [] for name, _ in routes}
+        for _ in range(GN_ROUNDS):
+            for name, extra in routes:
+                per[name].append((run(extra, 2 * GN_ITERATIONS) - run(extra, GN_ITERATIONS)) / GN_ITERATIONS)
+        say(f"  K = {K}: gauss_newton_solve per iteration (wall, {2 * GN_ITERATIONS} minus {GN_ITERATIONS} iterations, table read "
+            f"every {GN_CHECK}), rounds: " + "; ".join(
+                f"{name} {' '.join(f'{t:.3f}' for t in ts)} ms (mean {np.mean(ts):.3f}, spread {max(ts) - min(ts):.3f})"
+                for name, ts in per.items()) + f"; weighted / plain {np.mean(per[routes[1][0]]) / np.mean(per['plain']):.3f}")
+        del b, p, q
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
@@ -758,6 +840,7 @@ def main():
     ap.add_argument('--single-out', default=os.path.join(ROOT, 'profiles', 'reciprocal_single_times.txt'))
     ap.add_argument('--block-out', default=os.path.join(ROOT, 'profiles', 'block_products_times.txt'))
     ap.add_argument('--gnsolve-out', default=os.path.join(ROOT, 'profiles', 'gauss_newton_solve_times.txt'))
+    ap.add_argument('--weighted-out', default=os.path.join(ROOT, 'profiles', 'weighted_regulariser_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -863,11 +946,20 @@ def main():
             rec.forward()
             say(f"field_dtype='{name}': {rec!r}")
             gnsolve_block(rec, say, args.launches)
+            if name == 'double':                                # the regulariser does not see the kept fields' type
+                first = len(lines)
+                say(f"weighted regulariser, weights uniform in [0.2, 5], u standard normal, eps {GN_EPS}; norms "
+                    f"{', '.join(f'{a}: {b}' for a, b in GN_NORMS)}")
+                weighted_block(rec, say, args.launches)
+                weighted = lines[:2] + lines[first:]
+                del lines[first:]
             rec.release()
             del rec
         os.makedirs(os.path.dirname(os.path.abspath(args.gnsolve_out)), exist_ok=True)
         with open(args.gnsolve_out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
+        with open(args.weighted_out, 'w') as f:
+            f.write('\n'.join(weighted) + '\n')
         return
     if args.leg in ('hessian', 'gram'):
         rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
