@@ -626,7 +626,8 @@ class Hierarchy:
         """line_compact: True / False / 'auto' (default; or the environment's EMG3D_AMD_LINE_COMPACT) -- COMPACT line
         records: on the levels whose line passes stream their records through HBM (lines of ~128 blocks and more) the
         inverse blocks of the stored line factorisation and the forward pass's w records are kept in single precision
-        (all arithmetic, right-hand sides and solutions stay fp64): 890 instead of 1 210 B per block and colour pass,
+        (all arithmetic and the solutions stay fp64, and so do the right-hand sides but for the six entries of a line's
+        middle block, which pass through the single-precision w scratch): 890 instead of 1 210 B per block and colour pass,
         184 instead of 304 B of factor memory per cell and direction. The line solve is then a PERTURBED smoother
         (relative eps32 x cond of the 5 x 5 blocks), so every level must solve a correction equation: the coarse levels
         always do, the finest runs in residual form (``_cycle.run_cycles`` does that by itself on such a hierarchy; as

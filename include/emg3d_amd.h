@@ -101,7 +101,10 @@ typedef struct emg3d_level {
  * the finest level in residual form or as a Krylov preconditioner). The line passes that stream their records
  * through HBM (k_line_stream: lines of ~128 blocks and more) may then keep the inverse blocks T_k of the stored
  * factorisation and the forward pass's w records in SINGLE precision: values are rounded once when they are stored
- * and widened when they are loaded, every operation, every right-hand side and the solution stay fp64. The line
+ * and widened when they are loaded. The six right-hand-side entries r_Q of a line's middle block pass through the same
+ * single-precision w scratch and are rounded once too (6e-8 relative, not multiplied by cond). Every operation, every
+ * other right-hand side and the solution stay fp64. The fused kernel on shorter lines (k_line_colour) keeps the T_k in
+ * single precision only: its w records and all of its right-hand sides, r_Q included, live in LDS as fp64. The line
  * solve becomes (A_line (1 + O(eps32 cond(S_k))))^-1 -- a perturbation of the smoother, not of the equation: the
  * iteration converges to the same field at the same rate as long as eps32 x cond of the 5 x 5 blocks (~ 1 / (omega mu
  * sigma h^2)) stays well below the smoothing factor, which is the caller's to check (emg3d_amd.solver: cond <= 3e4).

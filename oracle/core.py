@@ -133,6 +133,12 @@ def gauss_seidel_z(ex, ey, ez, sx, sy, sz, eta_x, eta_y, eta_z, zeta, hx, hy,
         hx, hy, hz, nu, order)
 
 
+def set_eta_sum_round(on):
+    """Point smoother: round the six eta edge sums of a node to single precision before they enter the 6 x 6 system
+    (what the HIP library's tiled point smoother stores on correction levels). Off by default; not in the reference."""
+    lib().oracle_set_eta_sum_round(_ci(int(bool(on))))
+
+
 def blocks_to_amat(amat, bvec, middle, left, rhs, im, nc):
     """Reference emg3d/core.py:1351-1477 (``left`` is float64 there)."""
     dt = amat.dtype

@@ -261,6 +261,13 @@ static void FN(gs_node)(T *ex, T *ey, T *ez, const T *sx, const T *sy, const T *
     ORACLE_M_COEFFS
     ORACLE_ST_SUMS
 
+    /* the sums as a correction level of the HIP library stores them for its tiled point smoother: in single
+     * precision (both parts of a complex sum; a purely imaginary one has nothing else to round) */
+    if (oracle_eta_sum_round) {
+        st0 = ORACLE_ROUND32(st0); st1 = ORACLE_ROUND32(st1); st2 = ORACLE_ROUND32(st2);
+        st3 = ORACLE_ROUND32(st3); st4 = ORACLE_ROUND32(st4); st5 = ORACLE_ROUND32(st5);
+    }
+
     st[0] = st0 / 4.; st[1] = st1 / 4.; st[2] = st2 / 4.;
     st[3] = st3 / 4.; st[4] = st4 / 4.; st[5] = st5 / 4.;
 

@@ -72,20 +72,30 @@ void oracle_set_tile_order(const int *o) { int i; for (i = 0; i < 8; i++) oracle
 double oracle_omega = 1.0;
 void oracle_set_omega(double w) { oracle_omega = w; }
 
+/* The six eta edge sums of a node of the POINT smoother rounded to single precision before they enter the 6 x 6
+ * system -- what the HIP library's tiled point smoother keeps on correction levels (emg3d_amd/csrc/launch.h:
+ * PST_HALF_F32 / PST_FULL_F32). 0 (default) = the reference's sums. */
+int oracle_eta_sum_round = 0;
+void oracle_set_eta_sum_round(int on) { oracle_eta_sum_round = on; }
+
 #define PASTE_(a, b) a##b
 #define PASTE(a, b) PASTE_(a, b)
 
 /* real instantiation:  *_d */
 #define T double
 #define FN(name) PASTE(name, _d)
+#define ORACLE_ROUND32(v) ((double)(float)(v))
 #include "core_generic.h"
+#undef ORACLE_ROUND32
 #undef T
 #undef FN
 
 /* complex instantiation:  *_z */
 #define T double complex
 #define FN(name) PASTE(name, _z)
+#define ORACLE_ROUND32(v) ((double)(float)creal(v) + (double)(float)cimag(v) * I)
 #include "core_generic.h"
+#undef ORACLE_ROUND32
 #undef T
 #undef FN
 

@@ -33,6 +33,7 @@ int g_point_tile_min = 1 << 20;
 int g_line_order = 1;
 int g_line_wide = 0;
 int g_point_compact = 0;      // 1: the tile-major eta sums stored in single precision (kernels.hip: option point_compact)
+int g_line_only = -1;         // >= 0: the line sweeps run the pass of this colour class alone (tests/test_compact_model.py)
 int g_line_compact = 0;       // 1: T and w records of the line passes stored in single precision (kernels.hip: compact k_line_stream); 2: T only (k_line_colour)          // 1: the line passes in the wide form (stencil.h: line_wide_ref), where the level allows it
 
 // one sweep of the tiled point-smoother schedule: the eight tile-colour launches of
@@ -271,6 +272,7 @@ template <class T> void gs(const LevelArgs *lv, int lr, int nu, const void *xfac
         }
         for (int cc = 0; cc < 4; ++cc) {
             const int c = emg::line_sweep_colour(g_line_order, it, cc);
+            if (g_line_only >= 0 && c != g_line_only) continue;
             if (compact && g_line_compact == 2) {
                 if (lr == 1) line_colour_compact<T, 0, T>(L, c, facc.data(), lfac.data(), vec.data(), xvec.data());
                 else if (lr == 2) line_colour_compact<T, 1, T>(L, c, facc.data(), lfac.data(), vec.data(), xvec.data());
@@ -315,6 +317,7 @@ void emu_set_point_tile_min(int n) { g_point_tile_min = n; }
 void emu_set_line_order(int o) { g_line_order = o; }
 void emu_set_line_wide(int w) { g_line_wide = w; }
 void emu_set_line_compact(int c) { g_line_compact = c; }
+void emu_set_line_only(int c) { g_line_only = c; }
 void emu_set_point_compact(int c) { g_point_compact = c; }
 void emu_set_point_order(int o) { emg::point_order_ref() = o; }
 
@@ -326,6 +329,24 @@ void emu_gauss_seidel(const LevelArgs *lv, int lr, int nu)
 void emu_gauss_seidel_fac(const LevelArgs *lv, int lr, int nu, const void *fac, const double *lfac)
 {
     if (lv->is_complex) gs<cplx>(lv, lr, nu, fac, lfac); else gs<double>(lv, lr, nu, fac, lfac);
+}
+
+// the factor records of direction lr (1/2/3) as the CPU set-up stores them, in the layout of emg3d_dev_line_setup:
+// fac as T (compact = 0) or as compact_of<T> (compact = 1), lfac as double -- buffers of line_fac_elems / line_lfac_elems
+void emu_line_setup(const LevelArgs *lv, int lr, int compact, void *fac, double *lfac)
+{
+    auto run = [&](auto L, auto *f) {
+        using T = std::remove_cv_t<std::remove_reference_t<decltype(L.ex[0])>>;
+        using FT = std::remove_pointer_t<decltype(f)>;
+        if (lr == 1) line_setup_all<T, 0, FT>(L, f, lfac);
+        else if (lr == 2) line_setup_all<T, 1, FT>(L, f, lfac);
+        else line_setup_all<T, 2, FT>(L, f, lfac);
+    };
+    if (lv->is_complex) {
+        if (compact) run(to_level<cplx>(lv), (emg::compact_of<cplx>::type *)fac); else run(to_level<cplx>(lv), (cplx *)fac);
+    } else {
+        if (compact) run(to_level<double>(lv), (emg::compact_of<double>::type *)fac); else run(to_level<double>(lv), (double *)fac);
+    }
 }
 
 double emu_residual(const LevelArgs *lv, void *rx, void *ry, void *rz)

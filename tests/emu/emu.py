@@ -78,6 +78,24 @@ def gauss_seidel_fac(e, s, vm, lr, nu, fac, lfac):
     lib().emu_gauss_seidel_fac(ctypes.byref(lv), int(lr), int(nu), _ptr(fac), _ptr(lfac))
 
 
+def line_setup(e, s, vm, lr, compact=False):
+    """The T records of direction lr (1/2/3) as the CPU set-up stores them (layout of emg3d_dev_line_setup): 1-D array of
+    the field dtype, or of its single-precision counterpart with compact=True; and the coupling records (float64)."""
+    keep = []
+    lv = make_level(e, s, vm, keep)
+    cplx = e.fx.dtype == np.complex128
+    dt = (np.complex64 if cplx else np.float32) if compact else e.fx.dtype
+    nx, ny, nz = vm.grid.shape_cells
+    lines = {1: (ny - 1) * (nz - 1), 2: (nx - 1) * (nz - 1), 3: (nx - 1) * (ny - 1)}[lr]
+    n0 = (nx, ny, nz)[lr - 1]
+    pad = 2 if n0 <= 6 else 4                          # stencil.h: line_pad / line_mid / line_padded
+    mid = (n0 // 2) // pad * pad
+    n0p = mid + 2 + (n0 - 2 - mid + pad - 1) // pad * pad
+    fac, lfac = np.zeros(15 * n0p * lines, dt), np.zeros(8 * n0p * lines)
+    lib().emu_line_setup(ctypes.byref(lv), int(lr), int(bool(compact)), _ptr(fac), _ptr(lfac))
+    return fac, lfac
+
+
 def residual(e, s, vm, r=None):
     """Returns sum |r|^2; fills r (object with fx/fy/fz) if given."""
     keep = []
