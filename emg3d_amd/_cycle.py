@@ -9,8 +9,10 @@ emg3d/solver.py:471-649) is split here into
   HIP graph and replayed;
 * ``CoarseCorrection``: runs such a list on the chain of ``DeviceLevel`` objects (eagerly, or
   through a captured graph);
-* ``run_cycles``: the finest-level loop -- smoothing, coarse-grid correction, residual norm,
-  direction cycling, log lines and the termination rules (``StopRules``).
+* ``run_cycles`` / ``run_cycles_batch``: the finest-level loop for one right-hand side or for the
+  right-hand sides of a batch in lock step (one loop, ``_finest_level_cycles``) -- smoothing,
+  coarse-grid correction, residual norm, direction cycling, log lines and the termination rules
+  (``stop_reason`` / ``terminate``).
 
 The numbers it produces -- iteration counts, error histories, exit messages, log lines -- are
 the reference's; tests compare them.
@@ -22,7 +24,7 @@ import torch
 
 from emg3d_amd import _lib
 
-__all__ = ['run_cycles', 'coarse_correction', 'coarse_schedule', 'smooth_level', 'stop_reason',
+__all__ = ['run_cycles', 'run_cycles_batch', 'coarse_correction', 'coarse_schedule', 'smooth_level', 'stop_reason',
            'ConvergenceError', 'current_sc_dir', 'current_lr_dir']
 
 
@@ -62,7 +64,7 @@ def smooth_level(lv, nu, lr_dir, var):
     direction, e <- e_before + omega (e_after - e_before) (``solve(..., smoother_omega=)``; same fixed
     point, fewer cycles on models where the multi-colour ordering costs cycles)."""
     axes = _LR_AXES[current_lr_dir(lr_dir, lv.grid)]
-    omega = getattr(var, 'smoother_omega', 1.0)
+    omega = var.smoother_omega
     lv._factor_keep = axes             # (policy 'rebuild': the directions that should not make room)
     for lr in axes or (0,):
         if omega != 1.0:
@@ -194,7 +196,7 @@ def coarse_correction(clv, var, budget, first_level=1, graphed=None, top=None):
     # (the library's options select kernels and factor buffers: a graph captured under other
     # options would replay launches into buffers that may have been freed since)
     key = (int(var.sc_dir), int(var.lr_dir), budget, var.cycle, var.nu_pre, var.nu_post, var.nu_coarse, depth,
-           float(getattr(var, 'smoother_omega', 1.0)), _lib.options_fingerprint())
+           float(var.smoother_omega), _lib.options_fingerprint())
     entry = cache.get(key)
     if entry is None or entry['graph'] is None:
         if entry is None:
@@ -329,105 +331,150 @@ def record_cycle(var, l2_last, l2_prev):
 def run_cycles(top, var):
     """Multigrid cycles on the finest level until ``terminate`` says stop (or, for benchmarking,
     exactly ``var.fixed_cycles`` cycles). In place on ``top.e``; sets ``var.it``, ``var.l2`` and
-    the histories. (The finest-level part of emg3d/solver.py:512-649.)"""
-    loud = var.verb > 4
-    if var.first_cycle and var.verb > 3:
-        var.level_all.append(0)
-    # Residual form (solve(..., residual_form=); not for preconditioner calls, which are in that form
-    # already, nor for batches): every cycle solves A d = r = s - A e from d = 0 and adds d to e.
-    # For this linear, stationary iteration that is the same cycle in exact arithmetic; in floating
-    # point the errors of the smoothers -- the line solves multiply by stored block inverses: eps x
-    # cond of a block, relative to the right-hand side they are given -- then scale with the
+    the histories. As a preconditioner a failure raises ``ConvergenceError`` and leaves ``var.l2``
+    alone. (The finest-level part of emg3d/solver.py:512-649.)"""
+    _finest_level_cycles(top, var, [var], [True], batched=False)
+
+
+def run_cycles_batch(top, svar, vars_, active=None):
+    """``run_cycles`` for the ``top.batch`` right-hand sides of a batch in lock step: the structure of
+    the cycle (cycle type, sc/lr cycling, cycmax, nu_*; carried by ``svar``) does not depend on the
+    data, so one set of launches serves all; norms, stagnation histories, counters, log lines and
+    termination are per source (``vars_``), and every source gets the iterates, counts and histories
+    of its own ``run_cycles``. Returns (done, failed): the solution of every source as it was when
+    that source terminated (device tensors; None for sources that were not ``active``), and which
+    sources ended with a ``ConvergenceError`` (multigrid as preconditioner: diverged / stagnated)."""
+    svar.first_cycle = False        # (the level_all trace of the first cycle is a single solve's)
+    active = [True] * len(vars_) if active is None else list(active)
+    return _finest_level_cycles(top, svar, vars_, active, batched=True)
+
+
+def _finest_level_cycles(top, svar, vars_, active, batched):
+    """The finest-level loop. One right-hand side is ``vars_ == [svar]``; ``batched`` adds what only a
+    batch has -- a failing source is recorded instead of raising, a finished source's field is copied
+    out -- and drops what only a single solve has: the verbose lines (verb > 4) format one norm."""
+    loud = not batched and svar.verb > 4
+    solver = not svar.sslsolver         # (as a preconditioner the finest level solves a correction equation already)
+    if svar.first_cycle and svar.verb > 3:
+        svar.level_all.append(0)
+    # Residual form (solve(..., residual_form=)): every cycle solves A d = r = s - A e from d = 0 and
+    # adds d to e. For this linear, stationary iteration that is the same cycle in exact arithmetic; in
+    # floating point the errors of the smoothers -- the line solves multiply by stored block inverses:
+    # eps x cond of a block, relative to the right-hand side they are given -- then scale with the
     # residual, not with the field, and the iteration converges to round-off (DESIGN.md 4.3).
-    resform = bool(getattr(var, 'residual_form', False)) and not var.sslsolver and top.batch == 1
-    if (not resform and not var.sslsolver and top.batch == 1 and
-            getattr(top, 'uses_line_compact', lambda lines=True: False)(lines=bool(var.lr_cycle) or var.lr_dir != 0)):
+    resform = solver and bool(svar.residual_form)
+    if solver and not resform and top.uses_line_compact(lines=bool(svar.lr_cycle) or svar.lr_dir != 0):
         # compact line records (solver.Hierarchy(line_compact=...)): the streamed line solves are perturbed by
         # eps32 x cond, the finest level must see residuals, not the field
-        resform = var.residual_form = True
+        resform = True
+        for v in (svar, *vars_):
+            v.residual_form = True
+    may_switch = solver and svar.residual_form_auto
     if resform:
         top._b_valid = False
-    if getattr(top, '_resmode', None) is not None:      # (left behind by a solve that was interrupted: this solve's
-        top._resmode = None                             #  field and source are in the level's own buffers)
-    l2_last = top.residual(store=resform, norm=True)
-    ring = np.full(var.maxcycle, l2_last)           # errors one round of the schedule ago
-    var.cprint("     it cycmax               error", 4)
-    var.cprint("      level [  dimension  ]            info\n", 4)
+    top._resmode = None         # (whatever an interrupted solve left: this solve's field and source are in e and s)
+    l2 = np.atleast_1d(top.residual(store=resform, norm=True))      # one norm per right-hand side
+    ring = l2[:, None] * np.ones(svar.maxcycle)     # per source: the errors one round of the schedule ago
     if loud:
         n = top.grid.shape_cells
-        var.cprint(f"     {0:2} 0 {_level0_visits(var)} [{n[0]:3}, {n[1]:3}, {n[2]:3}]: {l2_last:.3e} initial error", 4)
-    if var.nu_init > 0:
-        smooth_level(top, var.nu_init, var.lr_dir, var)
+        svar.cprint("     it cycmax               error", 4)
+        svar.cprint("      level [  dimension  ]            info\n", 4)
+        svar.cprint(f"     {0:2} 0 {_level0_visits(svar)} [{n[0]:3}, {n[1]:3}, {n[2]:3}]: {l2[0]:.3e} initial error", 4)
+    done, failed = [None] * len(vars_), [False] * len(vars_)
+    # (the sweeps are counted on svar; `base + (svar - s0)` is an identity for a single solve)
+    base, s0 = [v.smoother_cell_sweeps for v in vars_], svar.smoother_cell_sweeps
+    if svar.nu_init > 0:
+        smooth_level(top, svar.nu_init, svar.lr_dir, svar)
         if loud:
-            _log_smoothing(var, 0, top, "initial smoothing", 0, _level0_visits(var))
+            _log_smoothing(svar, 0, top, "initial smoothing", 0, _level0_visits(svar))
         if resform:
             top.residual(store=True, norm=False)
-    fixed = getattr(var, 'fixed_cycles', None)
-    try:
-        _finest_level_loop(top, var, resform, l2_last, ring, fixed, loud)
-    finally:
-        _leave(top)             # (residual form: the field and the source back into the level's own buffers)
-
-
-def _finest_level_loop(top, var, resform, l2_last, ring, fixed, loud):
     it = 0
-    while True:
-        l2_prev = l2_last
-        ring[(it - 1) % var.maxcycle] = l2_last
-        entered = False
+    try:
+        while any(active):
+            l2_prev = l2
+            ring[:, (it - 1) % svar.maxcycle] = l2
+            _guarded_cycle(top, svar, resform, it, loud)
+            it += 1
+            l2 = np.atleast_1d(top.residual(store=resform, norm=True))
+            sc_run, lr_run = svar.sc_dir, svar.lr_dir           # what the log lines of this cycle show
+            if svar.sc_cycle:
+                svar.sc_dir = next(svar.sc_cycle)
+            if svar.lr_cycle:
+                svar.lr_dir = next(svar.lr_cycle)
+            sc_next, lr_next = svar.sc_dir, svar.lr_dir
+            stalled = []
+            for b, v in enumerate(vars_):
+                if not active[b]:
+                    continue
+                last, stag = float(l2[b]), float(ring[b, (it - 1) % svar.maxcycle])
+                v.it += 1
+                v.smoother_cell_sweeps = base[b] + (svar.smoother_cell_sweeps - s0)
+                v.sc_dir, v.lr_dir = sc_run, lr_run
+                record_cycle(v, last, float(l2_prev[b]))
+                v.sc_dir, v.lr_dir = sc_next, lr_next
+                if svar.fixed_cycles:
+                    finished = it >= svar.fixed_cycles
+                elif (may_switch and not resform and it < v.maxit and last < 1e-3 * v.l2_refe and
+                        stop_reason(v, last, stag, it) == ("STAGNATED", True) and _can_switch(top)):
+                    stalled.append(b)       # (not at its end: it goes on on the residual equation, below)
+                    continue
+                else:
+                    try:
+                        finished = terminate(v, last, stag, it)
+                    except ConvergenceError:
+                        if not batched:
+                            raise
+                        finished = failed[b] = True
+                if finished:
+                    active[b] = False
+                    v.l2 = last
+                    if batched:     # (only here: a single solve's field stays where it is, no field-sized copy)
+                        n = top.grid.n_edges
+                        done[b] = top.solution()[b * n:(b + 1) * n].clone()
+            if stalled:
+                # The direct form has stalled above the tolerance: the floor of the line smoothers' stored
+                # block inverses (or of the point smoother's pivots) on this model lies higher than the 'auto'
+                # rule of solver._residual_form predicted. The reference's banded LDL^T would go on converging;
+                # so do the cycles from here on, on the residual equation (their round-off scales with the
+                # residual). (An iteration that stagnates before it has gained three orders is not at a
+                # round-off floor.) The WHOLE batch goes on in that form -- one set of launches serves all
+                # right-hand sides --, so after a switch a source's arithmetic depends on its batch-mates: every
+                # source still active records it (info['residual_form'] == 'switched'); until then fields, counts
+                # and histories are those of separate solves. Stagnation is judged afresh, after another round of
+                # the direction schedule, only for the sources that stalled; the others keep their histories (a
+                # source that truly stagnates is still caught on time).
+                resform = svar.residual_form = True
+                top._b_valid = False
+                top.residual(store=True, norm=False)
+                ring[stalled, :] = np.inf
+                for b, v in enumerate(vars_):
+                    if active[b]:
+                        v.residual_form_switched = True
+                if not batched:
+                    svar.cprint(f"   > stalled at {l2[0] / svar.l2_refe:.1e} in direct form: continuing on the residual "
+                                "equation", 3)
+    finally:
+        top.leave_residual_form()       # (residual form: the field and the source back into the level's own buffers)
+    return done, failed
+
+
+def _guarded_cycle(top, var, resform, it, loud):
+    """One cycle (``_one_cycle``), in residual form on (e, s) = (d, r) between ``to_residual_equation`` and
+    ``from_residual_equation``: an interrupted one gives the caller's field and source back before it unwinds."""
+    if not resform:
+        _one_cycle(top, var, it, loud)
+        return
+    top.to_residual_equation()
+    try:
+        _one_cycle(top, var, it, loud)
+        top.from_residual_equation()
+    except BaseException:
         try:
-            if resform:
-                top.to_residual_equation()
-                entered = True
-            _one_cycle(top, var, it, loud)
-            if resform:
-                top.from_residual_equation()
-                entered = False
-        except BaseException:
-            if entered:        # (e, s) hold (d, r): give the caller's field and source back before unwinding
-                try:
-                    top.abandon_residual_equation()
-                except Exception:      # (a HIP error took the cycle down: the copies fail too -- the first error counts)
-                    pass
-            raise
-        it += 1
-        var.it += 1
-        l2_last = top.residual(store=resform, norm=True)
-        record_cycle(var, l2_last, l2_prev)
-        if var.sc_cycle:
-            var.sc_dir = next(var.sc_cycle)
-        if var.lr_cycle:
-            var.lr_dir = next(var.lr_cycle)
-        if fixed:
-            if it >= fixed:
-                break
-            continue
-        l2_stag = ring[(it - 1) % var.maxcycle]
-        reason = stop_reason(var, l2_last, l2_stag, it)
-        if (reason is not None and reason[0] == "STAGNATED" and it < var.maxit and l2_last < 1e-3 * var.l2_refe and
-                not resform and top.batch == 1 and
-                not var.sslsolver and getattr(var, 'residual_form_auto', False) and _can_switch(top)):
-            # The direct form has stalled above the tolerance: the floor of the line smoothers' stored
-            # block inverses (or of the point smoother's pivots) on this model lies higher than the 'auto'
-            # rule of solver._residual_form predicted. The reference's banded LDL^T would go on converging;
-            # so do the cycles from here on, on the residual equation (their round-off scales with the
-            # residual). Stagnation is judged afresh after another round of the direction schedule. (An
-            # iteration that stagnates before it has gained three orders is not at a round-off floor.)
-            resform = var.residual_form = var.residual_form_switched = True
-            top._b_valid = False
-            top.residual(store=True, norm=False)
-            ring[:] = np.inf
-            var.cprint(f"   > stalled at {l2_last / var.l2_refe:.1e} in direct form: continuing on the residual equation", 3)
-            continue
-        if terminate(var, l2_last, l2_stag, it):
-            break
-    var.l2 = l2_last
-
-
-def _leave(top):
-    leave = getattr(top, 'leave_residual_form', None)
-    if leave is not None:
-        leave()
+            top.abandon_residual_equation()
+        except Exception:      # (a HIP error took the cycle down: the copies fail too -- the first error counts)
+            pass
+        raise
 
 
 def _can_switch(top):

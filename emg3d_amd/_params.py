@@ -185,6 +185,17 @@ class MGParameters:
         self.do_return = True
         self.level_all, self.first_cycle = [], True      # levels visited in the first cycle (verb > 3)
         self.smoother_cell_sweeps = 0            # sum over smoother calls of nu * n_cells (not in the reference)
+        # what this package adds (not in the reference; set by solve / solve_batch / bench.py after construction)
+        self.smoother_omega = 1.0                # != 1: extrapolated smoothing calls (_cycle.smooth_level)
+        self.residual_form = False               # the finest level cycles on the residual equation
+        self.residual_form_auto = False          # ... or may switch to it when the direct form stalls
+        self.residual_form_switched = False      # ... and has done so
+        self.fixed_cycles = None                 # exactly this many cycles, no stop rules (benchmarking)
+        self.sparse_source = False               # the source goes up as its few non-zeros
+        self.device_source = False               # the source is in the hierarchy's source vector already
+        self.download = True                     # False: the result stays in the hierarchy's field only
+        self.line_compact = None                 # Hierarchy(line_compact=) of a hierarchy the solve builds itself
+        self.hierarchy_compact = False           # the hierarchy in use keeps compact coefficient records
 
         self._set_depths()
         self._set_directions(semicoarsening, linerelaxation)

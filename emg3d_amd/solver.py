@@ -24,7 +24,6 @@ from emg3d_amd._cycle import ConvergenceError as _ConvergenceError
 from emg3d_amd._cycle import current_lr_dir as _current_lr_dir
 from emg3d_amd._cycle import current_sc_dir as _current_sc_dir
 from emg3d_amd._cycle import one_liner as _print_one_liner
-from emg3d_amd._cycle import record_cycle as _print_cycle_info
 from emg3d_amd._cycle import smooth_level as _smooth
 from emg3d_amd._cycle import terminate as _terminate
 from emg3d_amd._device import DeviceLevel
@@ -280,10 +279,9 @@ _INFO = (('exit', lambda v: int(v.exit_message != 'CONVERGED')), ('exit_message'
          # addition of this package (not in the reference):
          ('smoother_cell_sweeps', lambda v: v.smoother_cell_sweeps),
          # the finest level ran (True), or ended up running ('switched'), on the residual equation
-         ('residual_form', lambda v: 'switched' if getattr(v, 'residual_form_switched', False)
-          else bool(getattr(v, 'residual_form', False))),
+         ('residual_form', lambda v: 'switched' if v.residual_form_switched else bool(v.residual_form)),
          # the hierarchy kept compact (single-precision) coefficient records on its large levels (Hierarchy.line_compact)
-         ('line_compact', lambda v: bool(getattr(v, 'hierarchy_compact', False))))
+         ('line_compact', lambda v: bool(v.hierarchy_compact)))
 
 
 def _info_dict(var):
@@ -303,7 +301,8 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
     the coarse levels cost what they cost for one source, and the factors are read once.
     Every source gets exactly the iterates, cycle count and field of its own
     ``solve(model, sfield, sslsolver=False, ...)``: a source that meets the tolerance is copied
-    out at that cycle while the others carry on.
+    out at that cycle while the others carry on (``_cycle.run_cycles_batch``, the loop of a single
+    solve with one set of stop rules per source).
 
     Returns a list of ``(efield, info_dict)``. Keyword arguments as ``solve`` (multigrid only),
     plus ``receivers`` (one ``(x, y, z, azimuth, elevation)`` for all sources or a list with
@@ -374,7 +373,7 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
         hier = hierarchy
     else:
         hier = Hierarchy(vmodel, batch=nb, line_compact=line_compact,
-                         point_compact_top=bool(var.sslsolver) or bool(getattr(svar, 'residual_form', False)))
+                         point_compact_top=bool(var.sslsolver) or bool(svar.residual_form))
     top = hier.top
     for v in vars_:
         v.hierarchy_compact = hier.line_compact
@@ -399,7 +398,7 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
     if var.sslsolver:
         done = _bicgstab_batch(hier, svar, vars_, nonzero)
     else:
-        done, _ = _multigrid_batch(top, svar, vars_, nonzero)
+        done, _ = _cycle.run_cycles_batch(top, svar, vars_, nonzero)
     out = []
     for b, (ef, v) in enumerate(zip(efields, vars_)):
         zero = v.l2_refe < 100 * np.finfo(float).tiny     # zero source: zero field (solver.py:372-379)
@@ -416,107 +415,6 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
                                                     device_field=None if zero or done[b] is None else done[b])
         out.append((ef if keep_fields else None, info))
     return out
-
-
-def _multigrid_batch(lv, svar, vars_, active=None):
-    """Level 0 of ``_multigrid`` for ``lv.batch`` right-hand sides in lock step: the structure
-    of the cycle (sc/lr cycling, cycmax; carried by ``svar``) does not depend on the data, so one
-    recursion serves all; norms, stagnation buffers, counters and termination are per source
-    (``vars_``). Returns (done, failed): the solution of every source as it was when that source
-    terminated (device tensors; None for sources that were not active), and which sources
-    ended with a ``_ConvergenceError`` (multigrid as preconditioner: diverged / stagnated)."""
-    nb = lv.batch
-    n = lv.grid.n_edges
-    cycmax = svar.cycmax
-    it = 0
-    # (finest level in residual form, as _cycle.run_cycles does it for one source)
-    resform = bool(getattr(svar, 'residual_form', False)) and not svar.sslsolver
-    may_switch = bool(getattr(svar, 'residual_form_auto', False)) and not svar.sslsolver
-    if not resform and not svar.sslsolver and lv.uses_line_compact(lines=bool(svar.lr_cycle) or svar.lr_dir != 0):
-        # (compact line records on this level: it must see residuals, as in _cycle.run_cycles)
-        resform = svar.residual_form = True
-        for v in vars_:
-            v.residual_form = True
-    if resform:
-        lv._b_valid = False
-    if getattr(lv, '_resmode', None) is not None:      # (left behind by an interrupted solve)
-        lv._resmode = None
-    l2_last = lv.residual(store=resform, norm=True)
-    l2_stag = np.ones((nb, svar.maxcycle)) * l2_last[:, None]
-    active = [True] * nb if active is None else list(active)
-    done = [None] * nb
-    failed = [False] * nb
-    base = [v.smoother_cell_sweeps for v in vars_]
-    s0 = svar.smoother_cell_sweeps
-    if svar.nu_init > 0:
-        _smooth(lv, svar.nu_init, svar.lr_dir, svar)
-        if resform:
-            lv.residual(store=True, norm=False)
-    while any(active):
-        l2_prev = l2_last.copy()
-        l2_stag[:, (it - 1) % svar.maxcycle] = l2_last
-        if resform:
-            lv.to_residual_equation()
-        if svar.nu_pre > 0:
-            _smooth(lv, svar.nu_pre, svar.lr_dir, svar)
-        sc_dir = _current_sc_dir(svar.sc_dir, lv.grid)
-        lv.residual(store=True, norm=False)
-        clv = lv.restrict_to(sc_dir)
-        _cycle.coarse_correction(clv, svar, cycmax, top=lv)       # eager, or the captured graph of this variant
-        lv.prolong_from(sc_dir)
-        if svar.nu_post > 0:
-            _smooth(lv, svar.nu_post, svar.lr_dir, svar)
-        it += 1
-        if resform:
-            lv.from_residual_equation()
-        l2_last = lv.residual(store=resform, norm=True)
-        sc_now, lr_now = svar.sc_dir, svar.lr_dir
-        if svar.sc_cycle:
-            svar.sc_dir = next(svar.sc_cycle)
-        if svar.lr_cycle:
-            svar.lr_dir = next(svar.lr_cycle)
-        switch, stalled = False, []
-        for b, v in enumerate(vars_):
-            if not active[b]:
-                continue
-            v.it += 1
-            v.smoother_cell_sweeps = base[b] + (svar.smoother_cell_sweeps - s0)
-            v.sc_dir, v.lr_dir = sc_now, lr_now           # what the log line of this cycle shows
-            _print_cycle_info(v, float(l2_last[b]), float(l2_prev[b]))
-            v.sc_dir, v.lr_dir = svar.sc_dir, svar.lr_dir
-            stag = float(l2_stag[b, (it - 1) % svar.maxcycle])
-            if may_switch and not resform and it < v.maxit:
-                # (as _cycle.run_cycles: a direct form that stalls above the tolerance goes on in residual form --
-                # here the whole batch does, from the next cycle on)
-                reason = _cycle.stop_reason(v, float(l2_last[b]), stag, it)
-                if reason is not None and reason[0] == "STAGNATED" and l2_last[b] < 1e-3 * v.l2_refe:
-                    switch = True
-                    stalled.append(b)
-                    continue
-            try:
-                finished = _terminate(v, float(l2_last[b]), stag, it)
-            except _ConvergenceError:
-                finished = failed[b] = True
-            if finished:
-                active[b] = False
-                v.l2 = float(l2_last[b])
-                done[b] = lv.solution()[b * n:(b + 1) * n].clone()      # (residual form: the accumulated field)
-        if switch and any(active):
-            # From the next cycle on the WHOLE batch cycles on the residual equation (one set of launches serves
-            # all right-hand sides): after a switch a source's arithmetic depends on its batch-mates -- every
-            # source still active records it (info['residual_form'] == 'switched'); until then fields, counts
-            # and histories are those of separate solves. Stagnation is judged afresh only for the sources that
-            # stalled; the others keep their histories (a source that truly stagnates is still caught on time).
-            resform = svar.residual_form = True
-            lv._b_valid = False
-            lv.residual(store=True, norm=False)
-            for b in stalled:
-                l2_stag[b, :] = np.inf
-            for b, v in enumerate(vars_):
-                if active[b]:
-                    v.residual_form_switched = True
-    lv.leave_residual_form()
-    return done, failed
 
 
 def _bicgstab_batch(hier, svar, vars_, nonzero):
@@ -537,7 +435,7 @@ def _bicgstab_batch(hier, svar, vars_, nonzero):
     def precondition(SRC, OUT, live_now):
         mover.copy(top.s, SRC)
         top.zero_field()
-        done, bad = _multigrid_batch(top, svar, vars_, live_now)
+        done, bad = _cycle.run_cycles_batch(top, svar, vars_, live_now)
         for b in range(nb):
             if live_now[b]:
                 mover.copy(OUT[b * n:(b + 1) * n], done[b])
@@ -715,17 +613,17 @@ def multigrid(model, sfield, efield, var, **kwargs):
     count in ``var.it``, final error in ``var.l2``. The level hierarchy lives in HBM for the
     duration of the call; pass ``hierarchy=`` (a ``Hierarchy``) to reuse one.
     """
-    hier = kwargs.get('hierarchy') or Hierarchy(model, line_compact=getattr(var, 'line_compact', None),
-                                                point_compact_top=bool(getattr(var, 'residual_form', False)))
+    hier = kwargs.get('hierarchy') or Hierarchy(model, line_compact=var.line_compact,
+                                                point_compact_top=bool(var.residual_form))
     var.hierarchy_compact = hier.line_compact
-    if getattr(var, 'device_source', False):
+    if var.device_source:
         hier.upload_field(efield)
     else:
-        hier.upload(sfield, efield, getattr(var, 'sparse_source', False))
+        hier.upload(sfield, efield, var.sparse_source)
     try:
         _multigrid(hier.top, var, 0, 0)
     finally:
-        if getattr(var, 'download', True):
+        if var.download:
             hier.download(efield)
 
 
@@ -759,7 +657,7 @@ def krylov(model, sfield, efield, var, hierarchy=None):
     """
     from emg3d_amd import _krylov
     # (as a preconditioner every level, the finest included, solves a correction equation)
-    hier = hierarchy or Hierarchy(model, line_compact=getattr(var, 'line_compact', None), point_compact_top=True)
+    hier = hierarchy or Hierarchy(model, line_compact=var.line_compact, point_compact_top=True)
     var.hierarchy_compact = hier.line_compact
     device_solver = {'bicgstab': _krylov.bicgstab, 'cgs': _krylov.cgs, 'gcrotmk': _krylov.gcrotmk}[var.sslsolver]
     try:
@@ -805,11 +703,11 @@ def _krylov_on_device(method, hier, sfield, efield, var):
     back into ``efield`` -- and into ``hier.top.e``, where receivers are read from."""
     top = hier.top
     b = torch.empty(top.e.numel(), dtype=top.e.dtype, device=hier.device)
-    if getattr(var, 'device_source', False):
+    if var.device_source:
         _lib.check(_lib.lib().emg3d_dev_copy(b.data_ptr(), top.s.data_ptr(), b.numel() * b.element_size(),
                                              torch.cuda.current_stream().cuda_stream), 'emg3d_dev_copy')
     else:
-        hier.put_source(sfield, b, getattr(var, 'sparse_source', False))
+        hier.put_source(sfield, b, var.sparse_source)
     x = torch.empty_like(b)
     if getattr(efield, '_is_zero', False):
         _lib.check(_lib.lib().emg3d_dev_zero(x.data_ptr(), x.numel() * x.element_size(),
@@ -819,7 +717,7 @@ def _krylov_on_device(method, hier, sfield, efield, var):
     status = method(hier, b, x, var, _cycle.run_cycles, lambda l2: _krylov_callback(var, l2))
     efield._is_zero = False
     top.e.copy_(x)          # the hierarchy's field is the solution (not the last preconditioner output)
-    if getattr(var, 'download', True):
+    if var.download:
         out = efield.field
         if out.flags.c_contiguous and out.flags.writeable:
             torch.from_numpy(out).copy_(x)
@@ -842,7 +740,7 @@ def smoothing(model, sfield, efield, nu, lr_dir):
     lv = _level_for(model, sfield, efield)
 
     class _V:
-        smoother_cell_sweeps = 0
+        smoother_cell_sweeps, smoother_omega = 0, 1.0
     _smooth(lv, nu, lr_dir, _V)
     efield.field[:] = lv.e.cpu().numpy()
 

@@ -2664,12 +2664,12 @@ def test_residual_form_converges_to_roundoff_with_an_air_layer():
     assert np.allclose(ia['error_at_cycle'], ib['error_at_cycle'], rtol=1e-5)
 
 
-def test_stalled_direct_form_continues_on_the_residual_equation():
-    """A solve whose direct-form cycles stall above the tolerance (found by tools/soak_same_order.py: 40^3,
-    stretched 1.15, blocky tri-axial model, 0.5 Hz, tol 1e-9 -- the direct form's floor is 1.7e-9 there, under
-    the 'auto' rule's radar) must not return STAGNATED where the reference converges: with residual_form='auto'
-    the cycling continues on the residual equation and converges; residual_form=False keeps the old behaviour;
-    the oracle (same ordering) converges in 10 cycles."""
+@pytest.fixture(scope='module')
+def stalled_case():
+    """The solve of test_stalled_direct_form_continues_on_the_residual_equation (found by tools/soak_same_order.py:
+    40^3, stretched 1.15, blocky tri-axial model, 0.5 Hz), the first tolerance under its direct form's floor with the
+    direct-form solve that stalls there, and the single 'on-stall' solve at that tolerance."""
+    import types
     rng = np.random.default_rng(83017)
     shape = (40, 40, 40)
     h = [widths(n // 2, n // 4, 25., 1.15) for n in shape]
@@ -2689,6 +2689,20 @@ def test_stalled_direct_form_continues_on_the_residual_equation():
             break
     assert tol is not None and infod['exit_message'] == 'STAGNATED' and infod['residual_form'] is False
     e, info = emg3d.solve(model, sfield, tol=tol, residual_form='on-stall', return_info=True, **kw)
+    # a second dipole on the same grid, for the batches
+    sf2 = emg3d.get_source_field(grid, (-30., 10., -20., 10., 5.), 0.5)
+    return types.SimpleNamespace(grid=grid, rho=rho, model=model, sfield=sfield, sf2=sf2, kw=kw, tol=tol, infod=infod,
+                                 e=e, info=info)
+
+
+def test_stalled_direct_form_continues_on_the_residual_equation(stalled_case):
+    """A solve whose direct-form cycles stall above the tolerance (found by tools/soak_same_order.py: 40^3,
+    stretched 1.15, blocky tri-axial model, 0.5 Hz, tol 1e-9 -- the direct form's floor is 1.7e-9 there, under
+    the 'auto' rule's radar) must not return STAGNATED where the reference converges: with residual_form='auto'
+    the cycling continues on the residual equation and converges; residual_form=False keeps the old behaviour;
+    the oracle (same ordering) converges in 10 cycles."""
+    c = stalled_case
+    grid, rho, model, sfield, kw, tol, e, info = c.grid, c.rho, c.model, c.sfield, c.kw, c.tol, c.e, c.info
     assert info['exit'] == 0 and info['residual_form'] == 'switched', (info['exit_message'], info['residual_form'])
     # ('auto': since the rule knows about the conductivity contrast it starts this model in residual form --
     # and then needs the oracle's number of cycles)
@@ -2707,12 +2721,27 @@ def test_stalled_direct_form_continues_on_the_residual_equation():
     _, i6 = emg3d.solve(model, sfield, tol=1e-6, return_info=True, **kw)
     assert i6['exit'] == 0 and i6['residual_form'] is False
     # in a batch the same happens for all its sources at once
-    sf2 = emg3d.get_source_field(grid, (-30., 10., -20., 10., 5.), 0.5)
-    out = emg3d.solve_batch(model, [sfield, sf2], tol=tol, residual_form='on-stall', **kw)
+    out = emg3d.solve_batch(model, [sfield, c.sf2], tol=tol, residual_form='on-stall', **kw)
     assert [i['exit'] for _, i in out] == [0, 0], [i['exit_message'] for _, i in out]
     assert relerr(out[0][0].field, eo.field) < 1e-8
-    outd = emg3d.solve_batch(model, [sfield, sf2], tol=tol, residual_form=False, **kw)
+    outd = emg3d.solve_batch(model, [sfield, c.sf2], tol=tol, residual_form=False, **kw)
     assert outd[0][1]['exit_message'] == 'STAGNATED'
+
+
+def test_stalled_source_of_a_batch_switches_like_its_single_solve(stalled_case):
+    """solve_batch(residual_form='on-stall') of the stalled source and a second dipole: the stalled source goes on
+    on the residual equation as in its own solve -- it converges, reports 'switched', and its field is the single
+    'on-stall' solve's to 1e-7 (until the switch the iterates are those of the single solve; after it the whole batch
+    cycles on the residual equation, from the cycle at which the first of its sources stalled)."""
+    c = stalled_case
+    assert c.info['exit'] == 0 and c.info['residual_form'] == 'switched'
+    out = emg3d.solve_batch(c.model, [c.sfield, c.sf2], tol=c.tol, residual_form='on-stall', **c.kw)
+    eb, ib = out[0]
+    d = relerr(eb.field, c.e.field)
+    print(f"stalled source in a batch of two: exit {ib['exit']} ({ib['exit_message']}), residual_form "
+          f"{ib['residual_form']!r}, {ib['it_mg']} cycles (single {c.info['it_mg']}), field vs single {d:.2e}")
+    assert ib['exit'] == 0 and ib['residual_form'] == 'switched', (ib['exit_message'], ib['residual_form'])
+    assert d < 1e-7, d
 
 
 def test_volume_average_adjoint_is_the_transpose():

@@ -528,41 +528,82 @@ def test_model_drops_a_device_snapshot_when_a_property_is_replaced():
     assert model._device_props == {'property_z': 'Z'}
 
 
-@pytest.mark.parametrize('auto', [True, False])
-def test_stall_switch_control_flow_without_a_gpu(auto, monkeypatch):
-    """_cycle.run_cycles: a direct form that stagnates above the tolerance goes on in residual form when the
-    caller left residual_form at 'auto' (and only then); scripted residual norms, no device."""
-    from emg3d_amd import _cycle
+class ScriptedLevel:
+    """A finest level without a device for the loop of emg3d_amd._cycle: `residual(norm=True)` returns scripted
+    norms, one script per right-hand side (a float for one, an array otherwise; a script that has run out repeats
+    its last value: the batch-mates cycle on), everything else records that it was called."""
+    _b_valid = True
+
+    def __init__(self, *scripts, fail_reserve=False):
+        import itertools
+        import types
+        import torch
+        self.batch = len(scripts)
+        self.norms = [itertools.chain(s, itertools.repeat(s[-1])) for s in scripts]
+        self.calls, self.fail_reserve = [], fail_reserve
+        self.grid = types.SimpleNamespace(n_edges=3, shape_cells=(8, 8, 8))
+        self.field = torch.zeros(3 * self.batch)
+
+    def residual(self, store=True, norm=False):
+        self.calls.append(('residual', store, norm))
+        if not norm:
+            return None
+        norms = [float(next(s)) for s in self.norms]
+        return norms[0] if self.batch == 1 else np.array(norms)
+
+    def uses_line_compact(self, lines=True):
+        return False
+
+    def reserve_residual_equation(self):          # (the two extra buffers, reserved before the switch)
+        import torch
+        self.calls.append('reserve')
+        if self.fail_reserve:
+            raise torch.cuda.OutOfMemoryError("scripted")
+
+    def solution(self):
+        return self.field
+
+    def to_residual_equation(self):
+        self.calls.append('to')
+
+    def from_residual_equation(self):
+        self.calls.append('from')
+
+    def abandon_residual_equation(self):
+        self.calls.append('abandon')
+
+    def leave_residual_form(self):
+        self.calls.append('leave')
+
+    def count(self, name):
+        return self.calls.count(name)
+
+
+def scripted_var(auto, resform, **kw):
     from emg3d_amd._params import MGParameters
-    script = [1.0, 1e-2, 1e-4, 1e-6, 1.1e-6, 1e-8, 1e-10, 1e-12]
-
-    class Top:
-        batch = 1
-        _b_valid = True
-
-        def __init__(self):
-            self.norms, self.calls = iter(script), []
-
-        def residual(self, store=True, norm=False):
-            self.calls.append(('residual', store, norm))
-            return next(self.norms) if norm else None
-
-        def reserve_residual_equation(self):          # (the two extra buffers, reserved before the switch)
-            self.calls.append('reserve')
-
-        def to_residual_equation(self):
-            self.calls.append('to')
-
-        def from_residual_equation(self):
-            self.calls.append('from')
-
-    monkeypatch.setattr(_cycle, '_one_cycle', lambda top, var, it, loud: top.calls.append('cycle'))
-    var = MGParameters(verb=0, sslsolver=False, semicoarsening=False, linerelaxation=False, shape_cells=(8, 8, 8),
-                       tol=1e-9, maxit=20)
+    opts = dict(verb=0, sslsolver=False, semicoarsening=False, linerelaxation=False, shape_cells=(8, 8, 8), tol=1e-9,
+                maxit=12)
+    var = MGParameters(**{**opts, **kw})
     var.l2_refe = 1.0
     var.error_at_cycle[0] = 1.0
-    var.residual_form, var.residual_form_auto = False, auto
-    top = Top()
+    var.residual_form, var.residual_form_auto = resform, auto
+    return var
+
+
+@pytest.fixture
+def recorded_cycles(monkeypatch):
+    from emg3d_amd import _cycle
+    monkeypatch.setattr(_cycle, '_one_cycle', lambda top, var, it, loud: top.calls.append('cycle'))
+    return _cycle
+
+
+@pytest.mark.parametrize('auto', [True, False])
+def test_stall_switch_control_flow_without_a_gpu(auto, recorded_cycles):
+    """_cycle.run_cycles: a direct form that stagnates above the tolerance goes on in residual form when the
+    caller left residual_form at 'auto' (and only then); scripted residual norms, no device."""
+    _cycle = recorded_cycles
+    var = scripted_var(auto, False, maxit=20)
+    top = ScriptedLevel([1.0, 1e-2, 1e-4, 1e-6, 1.1e-6, 1e-8, 1e-10, 1e-12])
     _cycle.run_cycles(top, var)
     if not auto:
         assert var.exit_message == 'STAGNATED' and var.it == 4 and 'to' not in top.calls
@@ -575,6 +616,132 @@ def test_stall_switch_control_flow_without_a_gpu(auto, monkeypatch):
     assert top.calls[first_to - 1] == ('residual', True, False) and top.calls[:first_to].count('cycle') == 4
     assert top.calls.index('reserve') < first_to
     assert top._b_valid is False
+
+
+# residual norms per cycle (the first is the initial one) -> cycles, exit message and final error of a multigrid solve
+# with tol 1e-9, maxit 12 and a fixed direction; A stalls at 1.1e-6: where the direct form may switch to the residual
+# equation ('auto', direct form) it goes on and converges
+STALLS = [1, 1e-2, 1e-4, 1e-6, 1.1e-6, 1e-8, 1e-10, 1e-12]
+SCRIPTED = {'A': (STALLS, 4, 'STAGNATED', 1.1e-6),
+            'B': ([1, 1e-3, 1e-6, 1e-9, 1e-12], 4, 'CONVERGED', 1e-12),
+            'C': ([1, .5, .25, .125, .2, .3, .4, .5], 4, 'STAGNATED', 0.2),
+            'D': ([1, .1, 20], 2, 'DIVERGED', 20),
+            'E': ([0.9 ** k for k in range(14)], 12, 'MAX. ITERATION REACHED, NOT CONVERGED', 0.9 ** 12)}
+
+
+@pytest.mark.parametrize('resform', [False, True])
+@pytest.mark.parametrize('auto', [True, False])
+def test_one_finest_level_loop_for_single_solves_and_batches(auto, resform, recorded_cycles):
+    """_cycle.run_cycles and _cycle.run_cycles_batch on scripted norms: every source of a batch gets the cycle count,
+    exit message, final error and histories of its own run (the values are those of the two loops this one replaced);
+    a stall switches the whole batch to the residual equation, and resets the stagnation history of the stalled
+    source only."""
+    _cycle = recorded_cycles
+    switches = auto and not resform
+    singles = []
+    for name, (script, it, message, l2) in SCRIPTED.items():
+        if name == 'A' and switches:
+            it, message, l2 = 6, 'CONVERGED', 1e-10
+        top, var = ScriptedLevel(script), scripted_var(auto, resform)
+        _cycle.run_cycles(top, var)
+        assert (var.it, var.exit_message, var.l2) == (it, message, l2), name
+        assert np.array_equal(var.error_at_cycle, np.array(script[:it + 1], dtype=float)), name
+        assert len(var.runtime_at_cycle) == it + 1, name
+        assert var.residual_form_switched is (name == 'A' and switches), name
+        cycles_in_resform = it if resform else 2 if name == 'A' and switches else 0
+        assert top.count('to') == top.count('from') == cycles_in_resform and top.count('cycle') == it, name
+        assert top.count('leave') == 1 and top.count('abandon') == 0, name
+        singles.append(var)
+    top = ScriptedLevel(*(case[0] for case in SCRIPTED.values()))
+    svar, vars_ = scripted_var(auto, resform), [scripted_var(auto, resform) for _ in SCRIPTED]
+    done, failed = _cycle.run_cycles_batch(top, svar, vars_)
+    assert failed == [False] * 5 and all(d is not None and d.shape == (3,) for d in done)
+    for name, v, single in zip(SCRIPTED, vars_, singles):
+        assert (v.it, v.exit_message, v.l2) == (single.it, single.exit_message, single.l2), name
+        assert np.array_equal(v.error_at_cycle, single.error_at_cycle), name
+        assert len(v.runtime_at_cycle) == len(single.runtime_at_cycle), name
+        # (the documented difference: E is still cycling when A stalls, and goes on with it on the residual equation)
+        assert v.residual_form_switched is (name in 'AE' and switches), name
+    assert top.count('cycle') == 12 and top.count('leave') == 1 and top.count('abandon') == 0
+    assert top.count('to') == top.count('from') == (12 if resform else 8 if switches else 0)
+    if switches:
+        # F stops gaining one cycle after A's stall: its history was not reset, so it ends there; A's was
+        top = ScriptedLevel(STALLS, [1, .5, .25, .125, .1, .2])
+        svar, vars_ = scripted_var(auto, resform), [scripted_var(auto, resform) for _ in range(2)]
+        _cycle.run_cycles_batch(top, svar, vars_)
+        assert [(v.it, v.exit_message, v.residual_form_switched) for v in vars_] == [(6, 'CONVERGED', True),
+                                                                                     (5, 'STAGNATED', True)]
+
+
+def test_finest_level_loop_as_a_preconditioner(recorded_cycles):
+    """Multigrid as a preconditioner (maxit = one round of the direction schedules = 3, no residual form): a failure
+    raises out of run_cycles and leaves var.l2 alone, in a batch it is recorded per source; reaching maxit is silent."""
+    _cycle = recorded_cycles
+    kw = dict(sslsolver=True, semicoarsening=True, linerelaxation=True)
+    scripts = ([1, .1, 20, 1], [1, .1, .01, .001, 1e-4], [1, 1e-10, 1e-11])
+    expected = [(2, 'DIVERGED', 20.0), (3, '', 1e-3), (1, 'CONVERGED', 1e-10)]
+    for script, (it, message, l2) in zip(scripts, expected):
+        top, var = ScriptedLevel(script), scripted_var(True, True, **kw)
+        assert var.maxit == 3
+        var.l2 = 77.0
+        if message == 'DIVERGED':
+            with pytest.raises(_cycle.ConvergenceError):
+                _cycle.run_cycles(top, var)
+            l2 = 77.0
+        else:
+            _cycle.run_cycles(top, var)
+        assert (var.it, var.exit_message, var.l2) == (it, message, l2)
+        assert top.count('cycle') == it and top.count('to') == 0 and top.count('leave') == 1
+    top = ScriptedLevel(*scripts)
+    svar, vars_ = scripted_var(True, True, **kw), [scripted_var(True, True, **kw) for _ in scripts]
+    done, failed = _cycle.run_cycles_batch(top, svar, vars_)
+    assert failed == [True, False, False] and all(d is not None and d.shape == (3,) for d in done)
+    assert [(v.it, v.exit_message, v.l2) for v in vars_] == expected
+    assert top.count('cycle') == 3 and top.count('to') == 0
+    # sources that are not active are left alone
+    top = ScriptedLevel(*scripts)
+    vars_ = [scripted_var(True, True, **kw) for _ in scripts]
+    done, failed = _cycle.run_cycles_batch(top, scripted_var(True, True, **kw), vars_, [False, False, True])
+    assert done[:2] == [None, None] and done[2] is not None and failed == [False] * 3
+    assert [v.it for v in vars_] == [0, 0, 1] and top.count('cycle') == 1
+
+
+@pytest.mark.parametrize('nb', [1, 3])
+def test_interrupted_residual_form_cycle_gives_field_and_source_back(nb, monkeypatch):
+    """An exception inside a cycle on the residual equation: (e, s) hold (d, r) then, and the level is told to give
+    the caller's field and source back -- once -- before the exception goes on, for one source and for a batch."""
+    from emg3d_amd import _cycle
+
+    def interrupted(top, var, it, loud):
+        raise KeyboardInterrupt
+    monkeypatch.setattr(_cycle, '_one_cycle', interrupted)
+    top = ScriptedLevel(*[SCRIPTED['E'][0]] * nb)
+    vars_ = [scripted_var(False, True) for _ in range(nb)]
+    with pytest.raises(KeyboardInterrupt):
+        if nb == 1:
+            _cycle.run_cycles(top, vars_[0])
+        else:
+            _cycle.run_cycles_batch(top, scripted_var(False, True), vars_)
+    assert top.count('to') == 1 and top.count('from') == 0 and top.count('abandon') == 1
+    assert top.calls.index('abandon') < top.calls.index('leave')
+
+
+@pytest.mark.parametrize('nb', [1, 3])
+def test_stall_without_memory_for_the_residual_equation_ends_stagnated(nb, recorded_cycles):
+    """The switch reserves the two extra field buffers first; without the memory for them the stalled source ends as
+    it would have without the switch, for one source and in a batch (whose other sources go on in direct form)."""
+    _cycle = recorded_cycles
+    scripts = [STALLS, SCRIPTED['B'][0], SCRIPTED['E'][0]][:nb]
+    top = ScriptedLevel(*scripts, fail_reserve=True)
+    vars_ = [scripted_var(True, False) for _ in range(nb)]
+    if nb == 1:
+        _cycle.run_cycles(top, vars_[0])
+    else:
+        _cycle.run_cycles_batch(top, scripted_var(True, False), vars_)
+    assert (vars_[0].it, vars_[0].exit_message, vars_[0].l2) == (4, 'STAGNATED', 1.1e-6)
+    assert top.count('reserve') == 1 and top.count('to') == 0 and top._b_valid is True
+    assert not any(v.residual_form_switched or v.residual_form for v in vars_)
+    assert [v.it for v in vars_] == [4, 4, 12][:nb]
 
 
 def test_fast_div_is_exact():
