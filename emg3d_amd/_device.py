@@ -34,6 +34,17 @@ def _ptr(t, offset_elems=0):
     return _vp(t.data_ptr() + offset_elems * t.element_size())
 
 
+def copy(dst, src):
+    """dst <- src on the current stream (device tensors of the same size)."""
+    _lib.check(_lib.lib().emg3d_dev_copy(_ptr(dst), _ptr(src), src.numel() * src.element_size(), _stream()),
+               'emg3d_dev_copy')
+
+
+def zero(t):
+    """t <- 0 (a fill kernel on the current stream)."""
+    _lib.check(_lib.lib().emg3d_dev_zero(_ptr(t), t.numel() * t.element_size(), _stream()), 'emg3d_dev_zero')
+
+
 def coarsen_flags(sc_dir):
     """(cx, cy, cz): is the direction coarsened for this sc_dir? (solver.py:891-897)"""
     return (sc_dir not in (1, 5, 6), sc_dir not in (2, 4, 6), sc_dir not in (3, 4, 5))
@@ -336,20 +347,23 @@ class DeviceLevel:
         """Copy e aside (for ``extrapolate_field``)."""
         if self.__dict__.get('_e_kept') is None:
             self._e_kept = torch.empty_like(self.e)
-        _lib.check(_lib.lib().emg3d_dev_copy(_ptr(self._e_kept), _ptr(self.e), self.e.numel() * self.e.element_size(),
-                                             _stream()), 'emg3d_dev_copy')
+        copy(self._e_kept, self.e)
 
-    def extrapolate_field(self, omega):
-        """e <- e_kept + omega (e - e_kept): one fused update (emg3d_dev_krylov_step with two
-        immediate coefficients; the level's reduction workspace doubles as its unused scalar table)."""
-        xs = (ctypes.c_void_p * 2)(self._e_kept.data_ptr(), self.e.data_ptr())
+    def _axpby(self, y, a, x0, b, x1):
+        """y <- a x0 + b x1: one fused update (emg3d_dev_krylov_step with two immediate coefficients; the
+        level's reduction workspace doubles as its unused scalar table)."""
+        xs = (ctypes.c_void_p * 2)(x0.data_ptr(), x1.data_ptr())
         slots = (ctypes.c_int * 2)(-1, -1)
-        scales = (ctypes.c_double * 2)(1.0 - omega, omega)
+        scales = (ctypes.c_double * 2)(a, b)
         none_p, none_i = (ctypes.c_void_p * 1)(), (ctypes.c_int * 1)()
         w = self.work
         _lib.check(_lib.lib().emg3d_dev_krylov_step(
-            self.e.numel(), int(self.is_complex), _ptr(self.e), 2, xs, slots, scales, 0, none_p, none_p, none_i, 0, none_i,
+            y.numel(), int(self.is_complex), _ptr(y), 2, xs, slots, scales, 0, none_p, none_p, none_i, 0, none_i,
             _ptr(w.ws), _ptr(w.ws), w.ws.numel(), _stream()), 'emg3d_dev_krylov_step')
+
+    def extrapolate_field(self, omega):
+        """e <- e_kept + omega (e - e_kept)."""
+        self._axpby(self.e, 1.0 - omega, self._e_kept, omega, self.e)
 
     # ---- finest level in residual form (_cycle.run_cycles): the cycle works on A d = r from d = 0
     def reserve_residual_equation(self):
@@ -374,13 +388,11 @@ class DeviceLevel:
     def to_residual_equation(self):
         """Before a cycle: r = s - A x is in ``self.r`` (residual(store=True)). First time: keeps the field and the
         source aside. Then s <- r (tensor swap), e <- 0."""
-        nbytes = self.e.numel() * self.e.element_size()
         self.reserve_residual_equation()
-        cp = _lib.lib().emg3d_dev_copy
         if self.__dict__.get('_resmode') is None:
-            _lib.check(cp(_ptr(self._x_kept), _ptr(self.e), nbytes, _stream()), 'emg3d_dev_copy')
+            copy(self._x_kept, self.e)
             if not self._b_valid:                 # the source of a solve does not change between its cycles
-                _lib.check(cp(_ptr(self._b_kept), _ptr(self.s), nbytes, _stream()), 'emg3d_dev_copy')
+                copy(self._b_kept, self.s)
                 self._b_valid = True
         self._swap_s_r()
         self.zero_field()
@@ -388,14 +400,7 @@ class DeviceLevel:
 
     def from_residual_equation(self):
         """After the cycle: x_kept += d (one fused update); the residual buffer is free again."""
-        xs = (ctypes.c_void_p * 2)(self._x_kept.data_ptr(), self.e.data_ptr())
-        slots = (ctypes.c_int * 2)(-1, -1)
-        scales = (ctypes.c_double * 2)(1.0, 1.0)
-        none_p, none_i = (ctypes.c_void_p * 1)(), (ctypes.c_int * 1)()
-        w = self.work
-        _lib.check(_lib.lib().emg3d_dev_krylov_step(
-            self.e.numel(), int(self.is_complex), _ptr(self._x_kept), 2, xs, slots, scales, 0, none_p, none_p, none_i, 0,
-            none_i, _ptr(w.ws), _ptr(w.ws), w.ws.numel(), _stream()), 'emg3d_dev_krylov_step')
+        self._axpby(self._x_kept, 1.0, self._x_kept, 1.0, self.e)
         self._swap_s_r()
         self._resmode = 'idle'
 
@@ -411,10 +416,8 @@ class DeviceLevel:
             return
         if mode == 'cycle':
             self._swap_s_r()
-        nbytes = self.e.numel() * self.e.element_size()
-        cp = _lib.lib().emg3d_dev_copy
-        _lib.check(cp(_ptr(self.e), _ptr(self._x_kept), nbytes, _stream()), 'emg3d_dev_copy')
-        _lib.check(cp(_ptr(self.s), _ptr(self._b_kept), nbytes, _stream()), 'emg3d_dev_copy')
+        copy(self.e, self._x_kept)
+        copy(self.s, self._b_kept)
         self._resmode = None
 
     def abandon_residual_equation(self):
@@ -464,9 +467,8 @@ class DeviceLevel:
         return w.sumsq
 
     def zero_field(self):
-        """e <- 0 (a fill kernel on the stream)."""
-        _lib.check(_lib.lib().emg3d_dev_zero(_ptr(self.e), self.e.numel() * self.e.element_size(), _stream()),
-                   'emg3d_dev_zero')
+        """e <- 0."""
+        zero(self.e)
 
     def pec_zero(self):
         """Zero the tangential components of e on the six boundary faces, for every right-hand side of the level."""

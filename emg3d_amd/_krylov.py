@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from emg3d_amd import _lib
-from emg3d_amd._device import _ptr, _stream
+from emg3d_amd._device import _ptr, _stream, copy
 
 _vp = ctypes.c_void_p
 DIV, MUL, NEG, COPY = 0, 1, 2, 3           # scalar instructions of emg3d_dev_krylov_step
@@ -100,83 +100,132 @@ class Vectors:
         return (out, ex.numpy().copy()) if extra is not None else out
 
     def copy(self, dst, src):
-        _lib.check(_lib.lib().emg3d_dev_copy(_ptr(dst), _ptr(src), src.numel() * src.element_size(), _stream()),
-                   'emg3d_dev_copy')
+        copy(dst, src)
 
 
-def _preconditioner(top, var, run_cycles, vec):
-    """out <- M vec: multigrid cycles on (source = vec, field = 0); identity without a cycle."""
+def _preconditioner(top, var, run_cycles):
+    """out <- M src: multigrid cycles on (source = src, field = 0); identity without a cycle."""
     def apply(src, out):
         if not var.cycle:
-            vec.copy(out, src)
+            copy(out, src)
             return
-        vec.copy(top.s, src)
+        copy(top.s, src)
         top.zero_field()
         run_cycles(top, var)            # maxit = one round of the direction schedule (solver.py:1376-1381)
-        vec.copy(out, top.e)
+        copy(out, top.e)
     return apply
 
 
-def bicgstab(hier, b, x, var, run_cycles, callback):
-    """Preconditioned BiCGSTAB (van der Vorst 1992). ``b``, ``x``: device vectors (x is updated
-    in place). ``callback(l2)`` after every iteration with the true residual norm. Returns the
-    SciPy status code."""
-    top = hier.top
-    V = Vectors(top)
-    psolve = _preconditioner(top, var, run_cycles, V)
-    r, v, t, p, phat, shat, rt = (V.new() for _ in range(7))
+def bicgstab_rows(top, B, X, tols, maxit, precondition, callback, live=None):
+    """Preconditioned BiCGSTAB (van der Vorst 1992) on ``len(tols)`` right-hand sides: the rows of the device
+    vectors ``B``, stacked like the fields of a batched level, with the start vectors in the rows of ``X``
+    (updated in place). Every row runs the iteration on its own, with its own scalar table, host scalars,
+    breakdown tests, stopping rule (``tols[b]``) and status code; what the rows share are the launches that
+    take them all at once -- per iteration two preconditioner applications (``precondition(SRC, OUT, live)``:
+    OUT <- M SRC for the live rows; it may clear ``live[b]`` for a row whose preconditioner failed, or raise),
+    two operator applications and the true residual norms, which ``callback(b, l2)`` gets after every
+    iteration of row b. ``live``: the rows that iterate (all by default; a row that stops is cleared in
+    place). Returns the SciPy status code of every row."""
+    nb = len(tols)
+    n = B.numel() // nb
+    live = [True] * nb if live is None else live
+    rows = lambda t, b: t[b * n:(b + 1) * n]           # noqa: E731
+    W = [Vectors(top, n) for _ in range(nb)]
+    R, V, T, P, PHAT, SHAT, RT = (torch.empty_like(B) for _ in range(7))
     eps = np.finfo(np.float64).eps
     rhotol = omegatol = eps ** 2
+    code = [maxit] * nb
+    atol, rr, rho, omega = ([0.0] * nb for _ in range(4))        # host scalars of every row
 
-    top.apply_A(x, r)
-    V.step(r, [(b, 1.0), (r, -1.0)], dots=[('bb', b, b)])
-    V.copy(rt, r)
-    V.step(None, dots=[('rr', r, r), ('rho', rt, r)])
-    bb, rr, rho = V.read('bb', 'rr', 'rho')
-    atol = max(1e-30, var.tol * np.sqrt(abs(bb)))
-    omega = alpha = 1.0
-    for iteration in range(var.ssl_maxit):
-        if np.sqrt(abs(rr)) < atol:
-            return 0
-        if abs(rho) < rhotol:
-            return -10
-        if iteration > 0:
-            if abs(omega) < omegatol:
-                return -11
-            V.step(p, [(r, 1.0), (p, 'beta'), (v, 'nbo')])      # p = r + beta (p - omega v)
-        else:
-            V.copy(p, r)
-        psolve(p, phat)
-        top.apply_A(phat, v)
-        # alpha = rho / (rt . v);  s = r - alpha v  (kept in r)
-        V.step(None, dots=[('rv', rt, v)], prog=[(DIV, 'alpha', 'rho', 'rv'), (NEG, 'nalpha', 'alpha', None)])
-        V.step(r, [(r, 1.0), (v, 'nalpha')], dots=[('ss', r, r)])
-        rv, ss, alpha = V.read('rv', 'ss', 'alpha')
-        if rv == 0:
-            return -11
-        if np.sqrt(abs(ss)) < atol:
-            V.step(x, [(x, 1.0), (phat, 'alpha')])
-            return 0
-        psolve(r, shat)
-        top.apply_A(shat, t)
-        # omega = (t . s) / (t . t);  x += alpha phat + omega shat;  r = s - omega t
-        V.step(None, dots=[('ts', t, r), ('tt', t, t)],
-               prog=[(DIV, 'omega', 'ts', 'tt'), (NEG, 'nomega', 'omega', None)])
-        V.step(x, [(x, 1.0), (phat, 'alpha'), (shat, 'omega')])
-        V.step(r, [(r, 1.0), (t, 'nomega')], dots=[('rr', r, r), ('rho_next', rt, r)],
-               prog=[(DIV, 'q1', 'rho_next', 'rho'), (DIV, 'q2', 'alpha', 'omega'), (MUL, 'beta', 'q1', 'q2'),
-                     (MUL, 'bo', 'beta', 'omega'), (NEG, 'nbo', 'bo', None), (COPY, 'rho', 'rho_next', None)])
-        sumsq = top.residual_sumsq(x, b)                 # the reference's callback: |b - A x|
-        (rr, rho, omega), l2 = V.read('rr', 'rho', 'omega', extra=sumsq)
-        callback(float(np.sqrt(l2[0])))
-    return var.ssl_maxit
+    def stop(b, status):
+        code[b], live[b] = status, False
+
+    top.apply_A(X, R)
+    for b in range(nb):
+        if live[b]:
+            W[b].step(rows(R, b), [(rows(B, b), 1.0), (rows(R, b), -1.0)], dots=[('bb', rows(B, b), rows(B, b))])
+            W[b].copy(rows(RT, b), rows(R, b))
+            W[b].step(None, dots=[('rr', rows(R, b), rows(R, b)), ('rho', rows(RT, b), rows(R, b))])
+    for b in range(nb):
+        if live[b]:
+            bb, rr[b], rho[b] = W[b].read('bb', 'rr', 'rho')
+            atol[b] = max(1e-30, tols[b] * np.sqrt(abs(bb)))
+    for iteration in range(maxit):
+        for b in range(nb):                              # ---- up to the first preconditioner call
+            if not live[b]:
+                continue
+            r, p, v = rows(R, b), rows(P, b), rows(V, b)
+            if np.sqrt(abs(rr[b])) < atol[b]:
+                stop(b, 0)
+            elif abs(rho[b]) < rhotol:
+                stop(b, -10)
+            elif iteration > 0 and abs(omega[b]) < omegatol:
+                stop(b, -11)
+            elif iteration > 0:
+                W[b].step(p, [(r, 1.0), (p, 'beta'), (v, 'nbo')])       # p = r + beta (p - omega v)
+            else:
+                W[b].copy(p, r)
+        if not any(live):
+            break
+        precondition(P, PHAT, live)
+        top.apply_A(PHAT, V)
+        for b in range(nb):                              # ---- between the two calls
+            if live[b]:
+                # alpha = rho / (rt . v);  s = r - alpha v  (kept in r)
+                r, v = rows(R, b), rows(V, b)
+                W[b].step(None, dots=[('rv', rows(RT, b), v)],
+                          prog=[(DIV, 'alpha', 'rho', 'rv'), (NEG, 'nalpha', 'alpha', None)])
+                W[b].step(r, [(r, 1.0), (v, 'nalpha')], dots=[('ss', r, r)])
+        for b in range(nb):
+            if not live[b]:
+                continue
+            rv, ss = W[b].read('rv', 'ss')
+            if rv == 0:
+                stop(b, -11)
+            elif np.sqrt(abs(ss)) < atol[b]:
+                W[b].step(rows(X, b), [(rows(X, b), 1.0), (rows(PHAT, b), 'alpha')])
+                stop(b, 0)
+        if not any(live):
+            break
+        precondition(R, SHAT, live)
+        top.apply_A(SHAT, T)
+        for b in range(nb):                              # ---- after the second call
+            if live[b]:
+                # omega = (t . s) / (t . t);  x += alpha phat + omega shat;  r = s - omega t
+                r, t, x = rows(R, b), rows(T, b), rows(X, b)
+                W[b].step(None, dots=[('ts', t, r), ('tt', t, t)],
+                          prog=[(DIV, 'omega', 'ts', 'tt'), (NEG, 'nomega', 'omega', None)])
+                W[b].step(x, [(x, 1.0), (rows(PHAT, b), 'alpha'), (rows(SHAT, b), 'omega')])
+                W[b].step(r, [(r, 1.0), (t, 'nomega')], dots=[('rr', r, r), ('rho_next', rows(RT, b), r)],
+                          prog=[(DIV, 'q1', 'rho_next', 'rho'), (DIV, 'q2', 'alpha', 'omega'), (MUL, 'beta', 'q1', 'q2'),
+                                (MUL, 'bo', 'beta', 'omega'), (NEG, 'nbo', 'bo', None), (COPY, 'rho', 'rho_next', None)])
+        sumsq = top.residual_sumsq(X, B)                 # the reference's callback: |b - A x|, all rows in one launch
+        l2 = None
+        for b in range(nb):
+            if live[b]:
+                if l2 is None:          # the first read brings the residual sums along in its one synchronising copy
+                    (rr[b], rho[b], omega[b]), l2 = W[b].read('rr', 'rho', 'omega', extra=sumsq)
+                else:
+                    rr[b], rho[b], omega[b] = W[b].read('rr', 'rho', 'omega')
+                callback(b, float(np.sqrt(l2[b])))
+    return code
+
+
+def bicgstab(hier, b, x, var, run_cycles, callback):
+    """``bicgstab_rows`` for one right-hand side: device vectors ``b``, ``x`` (the start vector, updated in
+    place), the preconditioner ``run_cycles(top, var)`` (the identity if ``var.cycle`` is None; what it raises
+    ends the solve), ``callback(l2)`` after every iteration with the true residual norm. Returns the SciPy
+    status code."""
+    psolve = _preconditioner(hier.top, var, run_cycles)
+    return bicgstab_rows(hier.top, b, x, [var.tol], var.ssl_maxit, lambda src, out, live: psolve(src, out),
+                         lambda _, l2: callback(l2))[0]
 
 
 def cgs(hier, b, x, var, run_cycles, callback):
     """Preconditioned CGS (Sonneveld 1989), as scipy.sparse.linalg.cgs iterates."""
     top = hier.top
     V = Vectors(top)
-    psolve = _preconditioner(top, var, run_cycles, V)
+    psolve = _preconditioner(top, var, run_cycles)
     r, rt, u, p, q, phat, vhat, uhat, tmp = (V.new() for _ in range(9))
     eps = np.finfo(np.float64).eps
     rhotol = eps ** 2
@@ -244,7 +293,7 @@ def gcrotmk(hier, b, x, var, run_cycles, callback, m=20, k=None):
     k = m if k is None else k
     nproj = m + 2 * k + 2                                 # Gram-Schmidt coefficients of one inner step
     V = Vectors(top, nslots=2 * nproj + 16)
-    psolve = _preconditioner(top, var, run_cycles, V)
+    psolve = _preconditioner(top, var, run_cycles)
     dt = np.complex128 if V.is_complex else np.float64
     a_names = [f'a{i}' for i in range(nproj)]             # projections of one inner step
     c_names = [f'c{i}' for i in range(nproj)]             # host coefficients of a linear combination
@@ -353,93 +402,3 @@ def gcrotmk(hier, b, x, var, run_cycles, callback, m=20, k=None):
         CU.append((cx, ux))
         del vs, zs
     return j_outer + 1
-
-
-def bicgstab_batch(hier, var_cycle, vars_, live, precondition, callback):
-    """BiCGSTAB for the ``top.batch`` right-hand sides of a batched hierarchy. Every source runs
-    the iteration of ``bicgstab`` above on its own rows with its own scalar table (its own
-    breakdown tests and stopping rule); what the sources share are the two preconditioner
-    applications (``precondition(SRC, OUT, live)``: multigrid cycles on all right-hand sides at
-    once; it clears ``live[b]`` for sources whose preconditioner failed) and the two operator
-    applications per iteration. ``live``: which sources iterate (updated in place).
-    Returns (X, codes): the solutions stacked like the fields, and the SciPy status per source."""
-    top = hier.top
-    nb, n = top.batch, top.grid.n_edges
-    rows = lambda t, b: t[b * n:(b + 1) * n]           # noqa: E731
-    W = [Vectors(top, n) for _ in range(nb)]
-    full = Vectors(top)
-    B, X = full.new(), full.new()
-    full.copy(B, top.s)
-    _lib.check(_lib.lib().emg3d_dev_zero(_ptr(X), X.numel() * X.element_size(), _stream()), 'emg3d_dev_zero')
-    R, V, T, P, PHAT, SHAT, RT = (full.new() for _ in range(7))
-    eps = np.finfo(np.float64).eps
-    rhotol = omegatol = eps ** 2
-    maxit = var_cycle.ssl_maxit
-    code = [maxit] * nb
-
-    top.apply_A(X, R)
-    atol, rr, rho, omega = [0.0] * nb, [0.0] * nb, [0.0] * nb, [1.0] * nb
-    for b in range(nb):
-        if not live[b]:
-            continue
-        W[b].step(rows(R, b), [(rows(B, b), 1.0), (rows(R, b), -1.0)], dots=[('bb', rows(B, b), rows(B, b))])
-        W[b].copy(rows(RT, b), rows(R, b))
-        W[b].step(None, dots=[('rr', rows(R, b), rows(R, b)), ('rho', rows(RT, b), rows(R, b))])
-    for b in range(nb):
-        if live[b]:
-            bb, rr[b], rho[b] = W[b].read('bb', 'rr', 'rho')
-            atol[b] = max(1e-30, vars_[b].tol * np.sqrt(abs(bb)))
-    for iteration in range(maxit):
-        for b in range(nb):                              # ---- up to the first preconditioner call
-            if not live[b]:
-                continue
-            r, p, v = rows(R, b), rows(P, b), rows(V, b)
-            if np.sqrt(abs(rr[b])) < atol[b]:
-                code[b], live[b] = 0, False
-            elif abs(rho[b]) < rhotol:
-                code[b], live[b] = -10, False
-            elif iteration > 0 and abs(omega[b]) < omegatol:
-                code[b], live[b] = -11, False
-            elif iteration > 0:
-                W[b].step(p, [(r, 1.0), (p, 'beta'), (v, 'nbo')])
-            else:
-                W[b].copy(p, r)
-        if not any(live):
-            break
-        precondition(P, PHAT, live)
-        top.apply_A(PHAT, V)
-        for b in range(nb):                              # ---- between the two calls
-            if live[b]:
-                r, v = rows(R, b), rows(V, b)
-                W[b].step(None, dots=[('rv', rows(RT, b), v)],
-                          prog=[(DIV, 'alpha', 'rho', 'rv'), (NEG, 'nalpha', 'alpha', None)])
-                W[b].step(r, [(r, 1.0), (v, 'nalpha')], dots=[('ss', r, r)])
-        for b in range(nb):
-            if not live[b]:
-                continue
-            rv, ss = W[b].read('rv', 'ss')
-            if rv == 0:
-                code[b], live[b] = -11, False
-            elif np.sqrt(abs(ss)) < atol[b]:
-                W[b].step(rows(X, b), [(rows(X, b), 1.0), (rows(PHAT, b), 'alpha')])
-                code[b], live[b] = 0, False
-        if not any(live):
-            break
-        precondition(R, SHAT, live)
-        top.apply_A(SHAT, T)
-        for b in range(nb):                              # ---- after the second call
-            if live[b]:
-                r, t, x = rows(R, b), rows(T, b), rows(X, b)
-                W[b].step(None, dots=[('ts', t, r), ('tt', t, t)],
-                          prog=[(DIV, 'omega', 'ts', 'tt'), (NEG, 'nomega', 'omega', None)])
-                W[b].step(x, [(x, 1.0), (rows(PHAT, b), 'alpha'), (rows(SHAT, b), 'omega')])
-                W[b].step(r, [(r, 1.0), (t, 'nomega')], dots=[('rr', r, r), ('rho_next', rows(RT, b), r)],
-                          prog=[(DIV, 'q1', 'rho_next', 'rho'), (DIV, 'q2', 'alpha', 'omega'), (MUL, 'beta', 'q1', 'q2'),
-                                (MUL, 'bo', 'beta', 'omega'), (NEG, 'nbo', 'bo', None), (COPY, 'rho', 'rho_next', None)])
-        sumsq = top.residual_sumsq(X, B)                 # all right-hand sides in one launch
-        l2 = np.sqrt(sumsq[:nb].cpu().numpy())
-        for b in range(nb):
-            if live[b]:
-                rr[b], rho[b], omega[b] = W[b].read('rr', 'rho', 'omega')
-                callback(b, float(l2[b]))
-    return X, code

@@ -455,7 +455,8 @@ def source_field_device(grid, points, frequency, strength=1.0, out=None):
     if out is None:
         out = torch.empty(grid.n_edges, dtype=dtype, device=dev)
     lib = _lib.lib()
-    _lib.check(lib.emg3d_dev_zero(_ptr(out), out.numel() * out.element_size(), _stream()), 'emg3d_dev_zero')
+    from emg3d_amd._device import zero
+    zero(out)
     pts = np.round(np.asarray(points, dtype=float), 9)
     geo = np.concatenate([grid.nodes_x, grid.nodes_y, grid.nodes_z, grid.h[0], grid.h[1], grid.h[2], pts.ravel()])
     g = torch.from_numpy(geo).to(dev)

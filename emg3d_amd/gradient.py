@@ -305,8 +305,8 @@ class Sensitivity:
     def _solve_forward(self, i):
         """Forward solve of pair i: (field in HBM -- a copy, the hierarchy's own buffer is reused --, responses)."""
         import torch
-        from emg3d_amd import _lib, solver
-        from emg3d_amd._device import _ptr, _stream
+        from emg3d_amd import solver
+        from emg3d_amd._device import copy
         sname, fname = self.pairs[i]
         freq = self.frequencies[fname]
         gkey, grid, gmodel, vol, plan = self._computational((sname, fname))
@@ -317,8 +317,7 @@ class Sensitivity:
                                 _sparse_source=True, **self.opts)
         self.n_solves['forward'] += 1
         e_fwd = torch.empty_like(top.e)
-        _lib.check(_lib.lib().emg3d_dev_copy(_ptr(e_fwd), _ptr(top.e), top.e.numel() * top.e.element_size(), _stream()),
-                   'emg3d_dev_copy')
+        copy(e_fwd, top.e)
         synthetic = fields.get_responses(Field(grid, frequency=freq), e_fwd, self._rec, 'linear', magnetic=self._mag)
         self.info.setdefault((sname, fname), {}).update(forward=finfo, backward=None, synthetic=synthetic)
         return e_fwd, synthetic

@@ -26,7 +26,7 @@ from emg3d_amd._cycle import current_sc_dir as _current_sc_dir
 from emg3d_amd._cycle import one_liner as _print_one_liner
 from emg3d_amd._cycle import smooth_level as _smooth
 from emg3d_amd._cycle import terminate as _terminate
-from emg3d_amd._device import DeviceLevel
+from emg3d_amd._device import DeviceLevel, copy as _copy, zero as _zero
 from emg3d_amd._params import MGParameters, Timer      # noqa: F401  (Timer: reference name utils.Timer)
 
 __all__ = ['solve', 'solve_batch', 'solve_source', 'multigrid', 'krylov', 'smoothing', 'restriction',
@@ -46,6 +46,7 @@ _SOLVE_EXTRAS = {'always_return': False, 'plain': False, 'efield': None, 'hierar
                  'smoother_omega': 1.0,       # != 1: extrapolated smoothing calls (_cycle.smooth_level)
                  'residual_form': 'auto',     # finest level in residual form (_cycle.run_cycles)
                  'line_compact': None}        # Hierarchy(line_compact=): compact records of the streamed line passes
+_ZERO_SOURCE = 100 * np.finfo(float).tiny     # a source with a norm below this is zero: zero field, nothing to solve
 
 
 def _residual_form(choice, var, model, sfield):
@@ -87,6 +88,21 @@ def _residual_form(choice, var, model, sfield):
         cond = np.float64(1.0) / np.float64(abs(complex(sfield.sval)) * fields.MU_0 * sig * hmin ** 2)
         cond = cond * np.float64(sig_max) / np.float64(sig)
     return bool(np.isfinite(cond) and np.finfo(float).eps * cond > 0.01 * var.tol)
+
+
+def _plain(*flags):
+    """``plain=True`` (plain multigrid): of sslsolver, semicoarsening, linerelaxation what was left at True goes off."""
+    return tuple(False if flag is True else flag for flag in flags)
+
+
+def _source_norm(sfield, vouched):
+    """(sparse, norm) of a host source field. sparse: it goes up as its few non-zero entries -- when the caller vouches
+    for an unmodified field, or when the field's dense buffer has never been handed out (fields.Field._untouched: a source
+    straight from get_source_field); norm and upload are then a dozen numbers instead of two passes over 1.2 GB."""
+    sparse = getattr(sfield, '_sparse', None) is not None and (vouched or getattr(sfield, '_untouched', False))
+    if sparse and not vouched:
+        sfield._assemble_on_device = False
+    return sparse, _host_norm(sfield._sparse[1] if sparse else sfield.field)
 
 
 def _check_omega(omega):
@@ -131,9 +147,8 @@ def solve(model, sfield, sslsolver=True, semicoarsening=True, linerelaxation=Tru
     keys plus ``smoother_cell_sweeps`` and ``residual_form``: False, True or 'switched').
     """
     extra = {name: kwargs.pop(name, default) for name, default in _SOLVE_EXTRAS.items()}
-    if extra['plain']:       # plain multigrid: whatever was left at its default is switched off
-        sslsolver, semicoarsening, linerelaxation = (
-            False if flag is True else flag for flag in (sslsolver, semicoarsening, linerelaxation))
+    if extra['plain']:
+        sslsolver, semicoarsening, linerelaxation = _plain(sslsolver, semicoarsening, linerelaxation)
     var = MGParameters(verb, sslsolver, semicoarsening, linerelaxation, model.shape, **kwargs)
     var.cprint(f"\n:: emg3d START :: {var.time.now} :: emg3d_amd (MI355X)\n", 2)
     var.cprint(var, 2)
@@ -146,13 +161,6 @@ def solve(model, sfield, sslsolver=True, semicoarsening=True, linerelaxation=Tru
     var.smoother_omega = _check_omega(extra['smoother_omega'])
     var.residual_form = _residual_form(extra['residual_form'], var, model, sfield)
     var.residual_form_auto = isinstance(extra['residual_form'], str)      # 'auto': may still switch on a stall
-    # the source as its few non-zero entries: when the caller vouches for an unmodified field (parallel.solve), or when
-    # the field's dense buffer has never been handed out (fields.Field._untouched: a source straight from
-    # get_source_field) -- its norm and its upload are then a dozen numbers instead of two passes over 1.2 GB
-    var.sparse_source = ((bool(extra['_sparse_source']) or getattr(sfield, '_untouched', False))
-                         and getattr(sfield, '_sparse', None) is not None)
-    if var.sparse_source and not extra['_sparse_source']:
-        sfield._assemble_on_device = False
     var.download = bool(extra['_download'])
     var.device_source = bool(extra['_device_source'])
     if var.device_source:
@@ -160,15 +168,14 @@ def solve(model, sfield, sslsolver=True, semicoarsening=True, linerelaxation=Tru
         # vector, and so is their norm
         if extra['hierarchy'] is None or extra['hierarchy'].top.batch != 1 or extra['efield'] is not None:
             raise ValueError("`_device_source` needs `hierarchy=` (batch 1) and no start field.")
-        var.sparse_source = False
-        var.l2_refe = float(_device_source_norms(extra['hierarchy'].top))
+        var.sparse_source, var.l2_refe = False, float(_device_source_norms(extra['hierarchy'].top))
     else:
-        var.l2_refe = _host_norm(sfield._sparse[1] if var.sparse_source else sfield.field)
+        var.sparse_source, var.l2_refe = _source_norm(sfield, bool(extra['_sparse_source']))
     var.error_at_cycle[0] = var.l2_refe
 
     vmodel = models.VolumeModel(model, sfield)
     efield, note = _start_field(model, vmodel, sfield, extra['efield'], extra['always_return'], var)
-    if var.l2_refe < 100 * np.finfo(float).tiny:         # zero source: zero field
+    if var.l2_refe < _ZERO_SOURCE:                       # zero source: zero field
         var.l2_refe = np.nan
         note = _nothing_to_do(var, "   > RETURN ZERO E-FIELD (provided sfield is zero)\n")
         efield = fields.Field(model.grid, dtype=sfield.dtype, frequency=sfield._frequency)
@@ -311,9 +318,8 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
     ``Hierarchy(vmodel, batch=len(sfields))`` of an earlier batch of the same frequency).
     """
     sslsolver = kwargs.pop('sslsolver', False)
-    if kwargs.pop('plain', False):       # as in solve(): only what was left at True is switched off
-        sslsolver, semicoarsening, linerelaxation = (
-            False if flag is True else flag for flag in (sslsolver, semicoarsening, linerelaxation))
+    if kwargs.pop('plain', False):
+        sslsolver, semicoarsening, linerelaxation = _plain(sslsolver, semicoarsening, linerelaxation)
     for k in ('efield', 'return_info', 'always_return'):
         kwargs.pop(k, None)
     receivers = kwargs.pop('receivers', None)            # one tuple for all, or one per source
@@ -385,23 +391,19 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
             v.error_at_cycle[0] = v.l2_refe
             efields.append(fields.Field(model.grid, dtype=sf.dtype, frequency=sf._frequency))
     for b, (sf, v) in enumerate(() if device_sources else zip(sfields, vars_)):
-        sparse = getattr(sf, '_sparse', None) is not None and (bool(getattr(sf, '_trust_sparse', False)) or
-                                                               getattr(sf, '_untouched', False))
-        if sparse and not getattr(sf, '_trust_sparse', False):
-            sf._assemble_on_device = False
-        v.l2_refe = _host_norm(sf._sparse[1] if sparse else sf.field)
+        sparse, v.l2_refe = _source_norm(sf, bool(getattr(sf, '_trust_sparse', False)))
         v.error_at_cycle[0] = v.l2_refe
         hier.put_source(sf, top.s[b * n:(b + 1) * n], sparse)
         efields.append(fields.Field(model.grid, dtype=sf.dtype, frequency=sf._frequency))
     top.zero_field()
-    nonzero = [v.l2_refe >= 100 * np.finfo(float).tiny for v in vars_]
+    nonzero = [v.l2_refe >= _ZERO_SOURCE for v in vars_]
     if var.sslsolver:
         done = _bicgstab_batch(hier, svar, vars_, nonzero)
     else:
         done, _ = _cycle.run_cycles_batch(top, svar, vars_, nonzero)
     out = []
     for b, (ef, v) in enumerate(zip(efields, vars_)):
-        zero = v.l2_refe < 100 * np.finfo(float).tiny     # zero source: zero field (solver.py:372-379)
+        zero = v.l2_refe < _ZERO_SOURCE                   # zero source: zero field
         if zero:
             v.exit_message = "CONVERGED"
             v.l2, v.l2_refe = 0.0, np.nan            # as solve() reports a zero source
@@ -419,7 +421,7 @@ def solve_batch(model, sfields, semicoarsening=True, linerelaxation=True, verb=0
 
 def _bicgstab_batch(hier, svar, vars_, nonzero):
     """BiCGSTAB with multigrid as preconditioner for the right-hand sides of a batch
-    (``_krylov.bicgstab_batch``: every source iterates with its own scalars; the preconditioner
+    (``_krylov.bicgstab_rows``: every source iterates with its own scalars; the preconditioner
     and operator applications are shared launches). Identical to separate solves as long as the
     sources run the same number of cycles inside every preconditioner call (the rule: ``maxit``
     cycles; a source may stop earlier on convergence) -- otherwise the sc/lr cycling of the shared
@@ -428,36 +430,39 @@ def _bicgstab_batch(hier, svar, vars_, nonzero):
     from emg3d_amd import _krylov
     top = hier.top
     nb, n = top.batch, top.grid.n_edges
-    live = list(nonzero)
     failed = [False] * nb
-    mover = _krylov.Vectors(top)
 
     def precondition(SRC, OUT, live_now):
-        mover.copy(top.s, SRC)
+        _copy(top.s, SRC)
         top.zero_field()
         done, bad = _cycle.run_cycles_batch(top, svar, vars_, live_now)
         for b in range(nb):
             if live_now[b]:
-                mover.copy(OUT[b * n:(b + 1) * n], done[b])
+                _copy(OUT[b * n:(b + 1) * n], done[b])
                 if bad[b]:
                     failed[b] = True
                     live_now[b] = False
 
-    X, code = _krylov.bicgstab_batch(hier, svar, vars_, live, precondition,
-                                     lambda b, l2: _krylov_callback(vars_[b], l2))
-    done = [None] * nb
+    B, X = torch.empty_like(top.s), torch.empty_like(top.s)
+    _copy(B, top.s)
+    _zero(X)
+    code = _krylov.bicgstab_rows(top, B, X, [v.tol for v in vars_], svar.ssl_maxit, precondition,
+                                 lambda b, l2: _krylov_callback(vars_[b], l2), live=list(nonzero))
     for b, v in enumerate(vars_):
-        if not nonzero[b]:
-            continue
-        if failed[b]:
-            v.exit_message += " (returned field is zero)"
-            continue
-        if code[b] < 0:
-            v.exit_message = v.exit_message or f"Error in {v.sslsolver} ({code[b]})"
-        else:
-            v.exit_message = "CONVERGED" if code[b] == 0 else "MAX. ITERATION REACHED, NOT CONVERGED"
-        done[b] = X[b * n:(b + 1) * n]
-    return done
+        if nonzero[b]:
+            _krylov_exit_message(v, code[b], failed[b])
+    return [X[b * n:(b + 1) * n] if nonzero[b] and not failed[b] else None for b in range(nb)]
+
+
+def _krylov_exit_message(var, status, failed):
+    """``var.exit_message`` from a Krylov solver's SciPy status. ``failed``: the preconditioner diverged or stagnated and
+    left its own message, which is kept (the reference's wording, emg3d/solver.py:767-770)."""
+    if failed:
+        var.exit_message += " (returned field is zero)"
+    elif status < 0:
+        var.exit_message = var.exit_message or f"Error in {var.sslsolver} ({status})"
+    else:
+        var.exit_message = "CONVERGED" if status == 0 else "MAX. ITERATION REACHED, NOT CONVERGED"
 
 
 def _host_norm(x):
@@ -660,11 +665,11 @@ def krylov(model, sfield, efield, var, hierarchy=None):
     hier = hierarchy or Hierarchy(model, line_compact=var.line_compact, point_compact_top=True)
     var.hierarchy_compact = hier.line_compact
     device_solver = {'bicgstab': _krylov.bicgstab, 'cgs': _krylov.cgs, 'gcrotmk': _krylov.gcrotmk}[var.sslsolver]
+    failed = False
     try:
         status = _krylov_on_device(device_solver, hier, sfield, efield, var)
     except _ConvergenceError:            # the preconditioner diverged or stagnated
-        status = -1
-        var.exit_message += " (returned field is zero)"      # (the reference's message, emg3d/solver.py:767-770)
+        status, failed = -1, True
         if getattr(efield, '_is_zero', False):
             # the zero field solve() made itself is what comes back
             efield.field[:] = 0
@@ -674,13 +679,8 @@ def krylov(model, sfield, efield, var, hierarchy=None):
             # reference, the assignment never happens); the device field follows it
             hier.upload_field(efield)
 
-    outcome = {True: "CONVERGED", False: "MAX. ITERATION REACHED, NOT CONVERGED"}
-    if status >= 0:
-        var.exit_message = outcome[status == 0]
-        lead = (50 * " " + "\r" if var.verb == 3 else "\n") + "   > "
-    else:
-        var.exit_message = var.exit_message or f"Error in {var.sslsolver} ({status})"
-        lead = "\n* ERROR   :: "
+    _krylov_exit_message(var, status, failed)
+    lead = (50 * " " + "\r" if var.verb == 3 else "\n") + "   > " if status >= 0 else "\n* ERROR   :: "
     var.cprint(lead + var.exit_message, 2)
 
 
@@ -704,14 +704,12 @@ def _krylov_on_device(method, hier, sfield, efield, var):
     top = hier.top
     b = torch.empty(top.e.numel(), dtype=top.e.dtype, device=hier.device)
     if var.device_source:
-        _lib.check(_lib.lib().emg3d_dev_copy(b.data_ptr(), top.s.data_ptr(), b.numel() * b.element_size(),
-                                             torch.cuda.current_stream().cuda_stream), 'emg3d_dev_copy')
+        _copy(b, top.s)
     else:
         hier.put_source(sfield, b, var.sparse_source)
     x = torch.empty_like(b)
     if getattr(efield, '_is_zero', False):
-        _lib.check(_lib.lib().emg3d_dev_zero(x.data_ptr(), x.numel() * x.element_size(),
-                                             torch.cuda.current_stream().cuda_stream), 'emg3d_dev_zero')
+        _zero(x)
     else:
         x.copy_(torch.from_numpy(np.ascontiguousarray(efield.field)))
     status = method(hier, b, x, var, _cycle.run_cycles, lambda l2: _krylov_callback(var, l2))

@@ -453,7 +453,7 @@ def test_poisoned_workspace_and_repeat(n, is_complex):
 @pytest.mark.parametrize('is_complex', KINDS)
 @pytest.mark.parametrize('n', ODD_SIZES)
 def test_row_slices_of_one_allocation(n, is_complex):
-    """Operands ``t[b n:(b + 1) n]`` with n odd, as ``bicgstab_batch`` passes them (a real row begins 8 bytes off a
+    """Operands ``t[b n:(b + 1) n]`` with n odd, as ``bicgstab_rows`` passes them (a real row begins 8 bytes off a
     16-byte boundary): the BiCGSTAB tail on the middle row of three equals the stand-alone reference, the rows before
     and after it keep their bits."""
     import torch
