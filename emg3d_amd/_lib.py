@@ -14,7 +14,7 @@ LIBPATH = os.path.join(LIBDIR, 'libemg3d_amd.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'emg3d_amd.h')
 SOURCES = [os.path.join(CSRC, f) for f in ('kernels.hip', 'stencil.h', 'launch.h', 'cplx.h', 'receivers.h', 'krylov.h',
                                             'adjoint.h', 'reciprocal.h', 'hessian.h', 'gram.h', 'block.h',
-                                            'regularise.h')] + [HEADER]
+                                            'regularise.h', 'precondition.h')] + [HEADER]
 
 # -ffp-contract: hipcc's own default for HIP, spelled out because csrc/kernels.hip switches contraction off for its
 # line-kernel section and back to THIS mode behind it (`#pragma clang fp contract(fast)`: the pragma can name a mode,
@@ -145,6 +145,11 @@ SIGNATURES = {
     'emg3d_dev_pcg_update': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 10 + [_sz, _vp]),
     'emg3d_dev_pcg_scalar': (_ci, [_sz, _ci, _ci, ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
     'emg3d_dev_pcg_direction': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 7),
+    'emg3d_dev_pcg_scale': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 3 + [_sz] + [_vp] * 3),
+    'emg3d_data_space_filter_ws_len': (_sz, [_ci, _ci]),
+    'emg3d_dev_data_space_filter': (_ci, [_ci, _ci, _ci] + [_vp] * 7 + [_sz, _vp]),
+    'emg3d_dev_pcg_finish': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 5 + [_sz] + [_vp] * 4 + [_sz, _vp]),
+    'emg3d_dev_pcg_direction_z': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 4),
     'emg3d_dev_source_field': (_ci, [_ci] * 4 + [_vp] * 7 + [_ci] + [ctypes.c_double] * 2 + [_vp] * 4),
     'emg3d_dev_volume_model': (_ci, [_ci] * 4 + [_vp] * 5 + [_ci] + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp] * 5),
     'emg3d_dev_magnetic_field': (_ci, [_ci] * 4 + [_vp] * 7 + [ctypes.c_double] * 2 + [_vp] * 4),

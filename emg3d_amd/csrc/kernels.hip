@@ -2837,3 +2837,4 @@ int emg3d_core_solve(void *amat, void *bvec, int n, int is_complex)
 #include "gram.h"
 #include "block.h"
 #include "regularise.h"
+#include "precondition.h"

@@ -620,8 +620,10 @@ class ReciprocalSensitivity(Sensitivity):
     R) x_k = b_k`` for K dampings at once by preconditioned CG on the device -- the K columns share every
     ``hessian_vec_block`` pass, the rest of an iteration is three fused kernels, the per-column scalars stay in a device
     table (``emg3d_dev_model_regulariser``, ``emg3d_dev_pcg_update`` / ``_scalar`` / ``_direction``, DESIGN.md 4.17);
-    ``regulariser_vec_block`` applies the smallness-plus-roughness operator ``R`` on its own. The outer inversion loop
-    (line search, observed data, choice of the damping) is the user's.
+    ``regulariser_vec_block`` applies the smallness-plus-roughness operator ``R`` on its own. Beside Jacobi it has a
+    data-space preconditioner, ``precondition='data'``: the Woodbury inverse of ``lambda_k diag R + J^T W J`` from one
+    ``data_gram`` and one eigen-decomposition per call, applied by one more pass over the kept fields.
+    The outer inversion loop (line search, observed data, choice of the damping) is the user's.
 
     field_dtype: ``'double'`` (default) keeps the fields as they are solved, ``n_edges x 16 B`` each. ``'single'``
         keeps them as complex64 (Laplace domain: float32): half the bytes in HBM or pinned memory, over PCIe with
@@ -1000,7 +1002,7 @@ class ReciprocalSensitivity(Sensitivity):
                               f"{free:,} B are free" + ("; a smaller `columns_per_pass` needs less." if rows > 1 else "."))
         return torch.empty((rows, stride), dtype=dtype, device=dev)
 
-    def _block_products(self, dev, kc, block=None, data=None, weights=None, reuse=None):
+    def _block_products(self, dev, kc, block=None, data=None, weights=None, reuse=None, apply=None):
         """The engine of ``jvec`` and ``jtvec`` (a block of one column, ``kc`` = 1) and of the three block methods,
         frequency by frequency with ONE ``_fields_of`` each. ``block``
         (device block): ``emg3d_dev_edge_weights`` per column and one ``emg3d_dev_sensitivity_dots_block`` per group of
@@ -1016,7 +1018,15 @@ class ReciprocalSensitivity(Sensitivity):
         ``reuse``: a dict that a caller of many passes of one shape (``gauss_newton_solve``) hands to every one of them:
         the uploaded weights and every scratch buffer are made by the first pass, kept in it and used again by the later
         ones (all passes run on one stream, in order), so that a pass uploads and allocates nothing of its own. The
-        kernels, their arguments and the results are those of a call without it."""
+        kernels, their arguments and the results are those of a call without it.
+
+        ``apply`` (with ``block`` alone; the set-up of ``_data_preconditioner_setup`` plus the PCG ``'table'``): the
+        data-space half of the data preconditioner between the two halves of the pass, in another order -- ALL
+        frequencies' ``dots_block`` first, their results gathered into the stacked real block (K, M) of ``stack_data`` by
+        torch index operations on those small tensors, ONE ``emg3d_dev_data_space_filter`` on it, then all frequencies'
+        ``combine_block`` with the coefficients ``conj`` of the filtered block, scattered back on the device. With
+        ``reuse`` it uploads nothing and the host waits for nothing between the kernels. ``keep='host'`` uploads each
+        frequency's stacks TWICE per application, once for each half. Without ``apply`` the function does what it did."""
         import torch
         from emg3d_amd import _lib
         from emg3d_amd._device import _ptr, _stream
@@ -1028,7 +1038,7 @@ class ReciprocalSensitivity(Sensitivity):
         per_freq = list(self._per_frequency())
         stride = max(f[3].n_edges for f in per_freq)
         stride += stride & 1                             # rows of float64 on 16-byte boundaries
-        combine = data is not None or weights is not None
+        combine = data is not None or weights is not None or apply is not None
         wbuf = tbufs = regridded = grad = None
         keep = {} if reuse is None else reuse            # (a dict of this call alone: nothing outlives it)
 
@@ -1057,59 +1067,52 @@ class ReciprocalSensitivity(Sensitivity):
                     if wf.any():                         # (a frequency whose weights are all zero: as hessian_diagonal)
                         wdevs[fname] = torch.from_numpy(np.ascontiguousarray(wf)).to(dev)
         jv = {}
-        for fname, mine, gkey, grid, vol, plan, smu0 in per_freq:
-            if weights is not None and fname not in wdevs:
-                continue
-            coef = None
-            if data is not None:
-                coef = np.zeros((K, len(mine), nrec), dtype=complex)
-                for k, vector in enumerate(data):
-                    for row, i in enumerate(mine):
-                        y = vector.get(self.pairs[i])
-                        if y is not None:
-                            coef[k, row] = np.conj(np.nan_to_num(np.asarray(y, dtype=complex), nan=0.0))
-                active = [k for k in range(K) if coef[k].any()]
-                if not active:
-                    continue
-            nx, ny, nz = grid.shape_cells
-            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
+
+        def stage(fname):
+            """A frequency's two stacks in HBM, whether they are complex, and the type of its edge vectors."""
             estack, xstack = self._fields_of(fname)
-            ns, nr = len(estack), len(xstack)
             is_complex = int(estack.is_complex())
             ftype = torch.complex128 if is_complex else torch.float64
             if combine and ftype not in tbufs:          # (before the kernels: the look at the free HBM is a host call)
                 tbufs[ftype] = self._block_scratch(kc, stride, ftype, dev, 'edge vectors')
-            if block is not None:
-                if gkey not in regridded:        # linear volume average: the map whose adjoint is the way back
-                    regridded[gkey] = torch.stack([torch.stack([plan.on_device(c, log=False) for c in col])
-                                                   for col in on_model])
-                cells = regridded[gkey]
-                # unit residual at a receiver: point source of strength conj(1 / (-s mu0)), times -s mu0 as every source
-                # (residual_source_field) = kappa p_r; jvec = p_r^T A^-1 (-s mu0 w e_s) = -s mu0 / kappa sum w e_s x_r
-                kappa = np.conj(1.0 / -smu0) * -smu0
-                scale = complex(-smu0 / kappa)
-                ws_len = L.emg3d_sensitivity_dots_block_ws_len(ns, nr, kc, n)
-                ws = kept(('ws', fname), lambda: torch.empty(ws_len, dtype=torch.float64, device=dev))
-                res = kept(('res', fname), lambda: torch.empty((K, ns, nr), dtype=ftype, device=dev))
-                dots, name = self._entry('emg3d_dev_sensitivity_dots_block', estack)
-                for g0 in range(0, K, kc):
-                    g1 = min(g0 + kc, K)
-                    for j in range(g0, g1):
-                        vx, vy, vz = (cells[j, k] for k in expand)
-                        w = wbuf[j - g0]
-                        _lib.check(L.emg3d_dev_edge_weights(nx, ny, nz, _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(w),
-                                                            _ptr(w, o1), _ptr(w, o2), _stream()), 'emg3d_dev_edge_weights')
-                    _lib.check(dots(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack), xstack.stride(0), nr,
-                                    _ptr(wbuf), stride, g1 - g0, scale.real, scale.imag, _ptr(res, g0 * ns * nr), _ptr(ws),
-                                    ws_len, _stream()), name)
-                jv[fname] = res
-            if not combine:
-                continue
-            if coef is not None:
-                cdev = torch.from_numpy(coef if is_complex else np.ascontiguousarray(coef.real)).to(dev)
-            else:
-                cdev = torch.conj_physical(jv[fname] * wdevs[fname]).contiguous()
-                active = list(range(K))
+            return estack, xstack, is_complex, ftype
+
+        def dots_half(f, staged):
+            fname, mine, gkey, grid, vol, plan, smu0 = f
+            estack, xstack, is_complex, ftype = staged
+            nx, ny, nz = grid.shape_cells
+            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
+            ns, nr = len(estack), len(xstack)
+            if gkey not in regridded:        # linear volume average: the map whose adjoint is the way back
+                regridded[gkey] = torch.stack([torch.stack([plan.on_device(c, log=False) for c in col])
+                                               for col in on_model])
+            cells = regridded[gkey]
+            # unit residual at a receiver: point source of strength conj(1 / (-s mu0)), times -s mu0 as every source
+            # (residual_source_field) = kappa p_r; jvec = p_r^T A^-1 (-s mu0 w e_s) = -s mu0 / kappa sum w e_s x_r
+            kappa = np.conj(1.0 / -smu0) * -smu0
+            scale = complex(-smu0 / kappa)
+            ws_len = L.emg3d_sensitivity_dots_block_ws_len(ns, nr, kc, n)
+            ws = kept(('ws', fname), lambda: torch.empty(ws_len, dtype=torch.float64, device=dev))
+            res = kept(('res', fname), lambda: torch.empty((K, ns, nr), dtype=ftype, device=dev))
+            dots, name = self._entry('emg3d_dev_sensitivity_dots_block', estack)
+            for g0 in range(0, K, kc):
+                g1 = min(g0 + kc, K)
+                for j in range(g0, g1):
+                    vx, vy, vz = (cells[j, k] for k in expand)
+                    w = wbuf[j - g0]
+                    _lib.check(L.emg3d_dev_edge_weights(nx, ny, nz, _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(w),
+                                                        _ptr(w, o1), _ptr(w, o2), _stream()), 'emg3d_dev_edge_weights')
+                _lib.check(dots(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack), xstack.stride(0), nr,
+                                _ptr(wbuf), stride, g1 - g0, scale.real, scale.imag, _ptr(res, g0 * ns * nr), _ptr(ws),
+                                ws_len, _stream()), name)
+            return res
+
+        def combine_half(f, staged, cdev, active):
+            fname, mine, gkey, grid, vol, plan, smu0 = f
+            estack, xstack, is_complex, ftype = staged
+            nx, ny, nz = grid.shape_cells
+            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
+            ns, nr = len(estack), len(xstack)
             tbuf = tbufs[ftype]
             combine_block, name = self._entry('emg3d_dev_sensitivity_combine_block', estack)
             for g0 in range(0, len(active), kc):
@@ -1126,6 +1129,54 @@ class ReciprocalSensitivity(Sensitivity):
                             nx, ny, nz, is_complex, _ptr(t), _ptr(t, o1), _ptr(t, o2), smu0.real, smu0.imag, _ptr(vol),
                             _ptr(gtarget), _ptr(gtarget, nc), _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_edges_to_cells')
                     self._on_model_grid(plan, grid, grad[j], to_cells)
+
+        if apply is not None:
+            # J^ u of ALL frequencies, the filter once on the stacked (K, M) block, then J^T y of all frequencies
+            M, rank, index = apply['n_data'], apply['rank'], apply['index']
+            live = [f for f in per_freq if f[0] in index]       # (a frequency whose weights are all zero has s = 0)
+            d = kept('d', lambda: torch.zeros((K, M), dtype=torch.float64, device=dev))
+            y = kept('y', lambda: torch.zeros((K, M), dtype=torch.float64, device=dev))
+            fws_len = L.emg3d_data_space_filter_ws_len(rank, K)
+            fws = kept('fws', lambda: torch.empty(fws_len, dtype=torch.float64, device=dev))
+            for f in live:
+                jv[f[0]] = dots_half(f, stage(f[0]))
+                parts = torch.view_as_real(jv[f[0]]).reshape(K, -1, 2)
+                d.index_copy_(1, index[f[0]][0], parts[:, :, 0])
+                d.index_copy_(1, index[f[0]][1], parts[:, :, 1])
+            _lib.check(L.emg3d_dev_data_space_filter(
+                M, rank, K, _ptr(apply['q']), _ptr(apply['eigenvalues']), _ptr(apply['s']), _ptr(d), _ptr(y),
+                _ptr(apply['table']), _ptr(fws), fws_len, _stream()), 'emg3d_dev_data_space_filter')
+            for f in live:
+                re, im = index[f[0]]
+                cdev = torch.complex(y[:, re], -y[:, im]).reshape(jv[f[0]].shape)       # conj, as for `data`
+                combine_half(f, stage(f[0]), cdev, list(range(K)))
+            return jv, grad
+        for f in per_freq:
+            fname, mine = f[0], f[1]
+            if weights is not None and fname not in wdevs:
+                continue
+            coef = None
+            if data is not None:
+                coef = np.zeros((K, len(mine), nrec), dtype=complex)
+                for k, vector in enumerate(data):
+                    for row, i in enumerate(mine):
+                        y = vector.get(self.pairs[i])
+                        if y is not None:
+                            coef[k, row] = np.conj(np.nan_to_num(np.asarray(y, dtype=complex), nan=0.0))
+                active = [k for k in range(K) if coef[k].any()]
+                if not active:
+                    continue
+            staged = stage(fname)
+            if block is not None:
+                jv[fname] = dots_half(f, staged)
+            if not combine:
+                continue
+            if coef is not None:
+                cdev = torch.from_numpy(coef if staged[2] else np.ascontiguousarray(coef.real)).to(dev)
+            else:
+                cdev = torch.conj_physical(jv[fname] * wdevs[fname]).contiguous()
+                active = list(range(K))
+            combine_half(f, staged, cdev, active)
         return jv, grad
 
     def _gradient_block(self, grad):
@@ -1455,9 +1506,151 @@ class ReciprocalSensitivity(Sensitivity):
         out = self._regulariser(self._regulariser_geometry(mask, dev), alphas, block, torch.empty_like(block), irls=irls)
         return out if (on_dev if on_device is None else on_device) else self.from_device(out)
 
+    def _regulariser_diagonal(self, geo, alphas, irls, dev):
+        """diag R on the device: (n_cells,) from ``emg3d_dev_model_regulariser_diagonal``, shared by the components, or,
+        with ``irls`` (of ``_upload_irls``), (n, n_cells) from ``emg3d_dev_model_regulariser_weighted_diagonal``."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        L = _lib.lib()
+        n, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
+        nx, ny, nz, hx, hy, hz, dmask = geo
+        if irls is None:
+            rd = torch.empty(ncell, dtype=torch.float64, device=dev)
+            _lib.check(L.emg3d_dev_model_regulariser_diagonal(
+                nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, None if dmask is None else _ptr(dmask), _ptr(rd),
+                _stream()), 'emg3d_dev_model_regulariser_diagonal')
+        else:                                                   # one diagonal of R per component
+            rd = torch.empty((n, ncell), dtype=torch.float64, device=dev)
+            _lib.check(L.emg3d_dev_model_regulariser_weighted_diagonal(
+                nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, None if dmask is None else _ptr(dmask),
+                *self._irls_args(irls, ncell), n, _ptr(rd), _stream()), 'emg3d_dev_model_regulariser_weighted_diagonal')
+        return rd
+
+    @staticmethod
+    def _check_data_rank(data_rank):
+        if data_rank is None:
+            return None
+        if isinstance(data_rank, bool) or not isinstance(data_rank, (int, np.integer)) or data_rank < 1:
+            raise ValueError(f"`data_rank` must be None or an integer >= 1. Provided: {data_rank!r}.")
+        return int(data_rank)
+
+    def _require_data_preconditioner(self):
+        """Raises unless ``precondition='data'`` can serve this survey: the limits of ``data_gram``, without a device."""
+        what = "gauss_newton_solve(precondition='data')"
+        self._require_model_grid(what, 'before the product is taken')
+        if self._data_rows() != 2:
+            raise NotImplementedError(f"{what}: frequency-domain surveys only; in the Laplace domain `jvec` is minus the "
+                                      "adjoint of `jtvec` (see `data_gram`) and the identity behind the preconditioner "
+                                      "changes its signs.")
+
+    def _data_preconditioner_setup(self, dev, w, rd, dmask, data_rank):
+        """The set-up of the data-space preconditioner from the checked weights ``w``, the device
+        diagonal ``rd`` of R ((n_cells,) or (n, n_cells)) and the device mask: ``dinv`` = 1 / rd on active cells (1 where
+        rd is not positive, 0 on inactive cells), ``G0 = J^ diag(dinv) J^T`` by ``_data_gram_block``, ``s`` = the square
+        roots of the weights in the ordering of ``stack_data``, and on the host, in fp64, ``eigh`` of ``B = diag(s) G0
+        diag(s)``: negative eigenvalues are set to 0 and the ``min(data_rank, M)`` largest pairs kept. A dict: in HBM
+        ``dinv`` (rows ``dinv_stride`` apart), ``q`` (M, rank), ``eigenvalues`` (rank, descending), ``s`` (M) and per
+        frequency with a weight > 0 the positions ``index[name] = (Re, Im)`` of its data in the stacked vector; on the
+        host ``q_host``, ``eigenvalues_host`` (all M, descending, clipped), ``s_host``; ``n_data``, ``rank``; ``seconds``
+        of the four steps gram / download / eigh / upload."""
+        import time
+        import torch
+        n, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
+        nrec, npair = len(self._rec[0]), len(self.pairs)
+
+        def lap(since=None):
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            return now if since is None else (now, now - since)
+        seconds = {}
+        clock = lap()
+        rows = rd.view(-1, ncell)
+        dinv = torch.where(rows > 0, 1.0 / rows, torch.ones_like(rows))
+        if dmask is not None:
+            dinv = torch.where(dmask != 0, dinv, torch.zeros_like(dinv))
+        dinv = dinv.contiguous()
+        d = self._chain_factors(dev)
+        G0 = self._data_gram_block((dinv.expand(n, ncell) * (d * d)).contiguous(), 2, dev)
+        clock, seconds['gram'] = lap(clock)
+        G0 = G0.cpu().numpy()
+        clock, seconds['download'] = lap(clock)
+        s = np.sqrt(np.tile(np.concatenate([w[pair] for pair in self.pairs]), 2))
+        M = len(s)
+        rank = M if data_rank is None else min(data_rank, M)
+        eig, Q = np.linalg.eigh(s[:, None] * G0 * s[None, :])
+        eig, Q = np.maximum(eig[::-1], 0.0), Q[:, ::-1]
+        q_host, eig_host = np.ascontiguousarray(Q[:, :rank]), np.ascontiguousarray(eig[:rank])
+        clock, seconds['eigh'] = lap(clock)
+        index = {}
+        for fname, mine, *_ in self._per_frequency():
+            if np.stack([w[self.pairs[i]] for i in mine]).any():
+                re = torch.tensor([i * nrec + r for i in mine for r in range(nrec)], dtype=torch.int64, device=dev)
+                index[fname] = (re, re + npair * nrec)
+        up = [torch.from_numpy(a).to(dev) for a in (q_host, eig_host, s)]
+        clock, seconds['upload'] = lap(clock)
+        return {'dinv': dinv, 'dinv_stride': ncell if len(dinv) > 1 else 0, 'q': up[0], 'eigenvalues': up[1], 's': up[2],
+                'index': index, 'n_data': M, 'rank': rank, 'q_host': q_host, 'eigenvalues_host': eig, 's_host': s,
+                'seconds': seconds}
+
+    def _apply_data_preconditioner(self, pre, dev, kc, first, r, u, z, dmask, pq, ws, reuse):
+        """``z = M r`` for the running columns of ``pre['table']``: ``emg3d_dev_pcg_scale`` (u), one application pass of
+        ``_block_products`` (g = J^T y), ``emg3d_dev_pcg_finish`` (z, and the partial sums of <r, z> and <r, r> in
+        ``ws`` for ``emg3d_dev_pcg_scalar``). All blocks (K, n, n_cells) on the device; queued, nothing is waited for."""
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
+        L = _lib.lib()
+        K, n, ncell = r.shape
+        pqp = None if pq is None else _ptr(pq)
+        _lib.check(L.emg3d_dev_pcg_scale(ncell, n, K, first, _ptr(u), _ptr(r), _ptr(pre['dinv']), pre['dinv_stride'],
+                                         _ptr(pre['table']), pqp, _stream()), 'emg3d_dev_pcg_scale')
+        g = self._gradient_block(self._block_products(dev, kc, block=u, reuse=reuse, apply=pre)[1])
+        _lib.check(L.emg3d_dev_pcg_finish(ncell, n, K, first, _ptr(z), _ptr(u), _ptr(g), _ptr(r), _ptr(pre['dinv']),
+                                          pre['dinv_stride'], None if dmask is None else _ptr(dmask), _ptr(pre['table']),
+                                          pqp, _ptr(ws), ws.numel(), _stream()), 'emg3d_dev_pcg_finish')
+        return z
+
+    def _data_preconditioner(self, dampings, weights=None, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None,
+                             data_rank=None, columns_per_pass=8, *, cell_weights=None, norms=None, linearise_at=None,
+                             irls_eps=None):
+        """The data-space preconditioner of ``gauss_newton_solve(precondition='data')`` on its own, arguments as there:
+        ``(setup, apply)`` with the dict of ``_data_preconditioner_setup`` and ``apply(block)``, which returns ``M_k
+        block[k]`` for the K = ``len(dampings)`` columns of a device block as a new device block, through the kernels
+        and the pass of the solve."""
+        import torch
+        from emg3d_amd import _lib
+        kc = self._check_columns(columns_per_pass)
+        lam = self._check_dampings(dampings)
+        alphas = self._check_regulariser(smallness, smoothness)
+        mask = self._check_active(active)
+        irls = self._check_irls(cell_weights, norms, linearise_at, irls_eps)
+        data_rank = self._check_data_rank(data_rank)
+        w = self._check_weights(weights)
+        self._require_data_preconditioner()
+        dev = self._device()
+        self.forward()
+        L = _lib.lib()
+        K, ncell = len(lam), self.model.grid.n_cells
+        geo = self._regulariser_geometry(mask, dev)
+        pre = self._data_preconditioner_setup(dev, w, self._regulariser_diagonal(geo, alphas, self._upload_irls(irls, dev), dev),
+                                              geo[6], data_rank)
+        host = np.zeros((K, L.emg3d_pcg_table_len(K) // K))
+        host[:, 0] = lam
+        pre['table'] = torch.from_numpy(host).to(dev)
+        ws = torch.empty(L.emg3d_pcg_ws_len(ncell, K), dtype=torch.float64, device=dev)
+        reuse = {}
+
+        def apply(block):
+            r = self._check_device_block(block, dev)
+            if len(r) != K:
+                raise ValueError(f"the block must have K = len(dampings) = {K} columns. Provided: {len(r)}.")
+            return self._apply_data_preconditioner(pre, dev, kc, 1, r, torch.zeros_like(r), torch.zeros_like(r), geo[6], None,
+                                                   ws, reuse)
+        return pre, apply
+
     def gauss_newton_solve(self, rhs, dampings, weights=None, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None,
                            tol=1e-3, maxit=50, precondition=True, check_every=4, on_device=None, columns_per_pass=8, *,
-                           cell_weights=None, norms=None, linearise_at=None, irls_eps=None):
+                           cell_weights=None, norms=None, linearise_at=None, irls_eps=None, data_rank=None):
         """The inner linear solve of a Gauss-Newton step for K dampings at once: column ``k`` solves
 
             (Re(J^H W J) + dampings[k] R) x_k = b_k
@@ -1483,7 +1676,21 @@ class ReciprocalSensitivity(Sensitivity):
             the inversion.
         precondition: Jacobi, ``1 / (hessian_diagonal(weights) + dampings[k] diag R)``, formed inside the kernels from
             the two diagonals, which all columns share (where that sum is not positive: 1). Needs every computational
-            grid to be the model grid, as ``hessian_diagonal`` does. False: no preconditioner.
+            grid to be the model grid, as ``hessian_diagonal`` does. False: no preconditioner. ``'data'``: the data-space
+            (Woodbury) preconditioner. ``H = J^T W J`` has rank at most M, the number of real data, so
+            ``(lambda_k diag R + H)^-1`` is ``diag R^-1 / lambda_k`` minus a correction through an M x M matrix: once
+            per call ``data_gram(1 / diag R)`` is formed, scaled by the square roots of the weights and decomposed on the
+            host (``numpy.linalg.eigh``, fp64) -- ONE decomposition serves all K dampings, which only change the filter
+            ``lambda_k / (lambda_k + eigenvalue)``. It is exact when ``R`` is diagonal (smallness only: one iteration);
+            otherwise only the off-diagonal part of ``lambda R`` is left to the iteration. An application is one more
+            block pass over the kept fields (``emg3d_dev_pcg_scale``, ``dots_block``, ``emg3d_dev_data_space_filter``,
+            ``combine_block``, ``emg3d_dev_pcg_finish``; then ``emg3d_dev_pcg_direction_z``), so an iteration costs
+            about twice a Jacobi one. It has the limits of ``data_gram``: every computational grid must be the model
+            grid, frequency-domain surveys only; the set-up costs ``eigh`` of an M x M matrix on the host.
+        data_rank (keyword only; ignored unless ``precondition='data'``): ``None`` or an integer >= 1: keep only the
+            ``min(data_rank, M)`` largest eigenpairs. The preconditioner is then the exact inverse of ``lambda_k diag R``
+            plus the rank-``data_rank`` part of ``H``: symmetric positive definite for every rank, and PCG needs about one
+            more iteration per eigenvalue left out.
         check_every: the host reads the table of the per-column scalars (64 B per column) every so many iterations --
             the only download inside the loop -- and stops when no column is running, or at ``maxit``. A column that
             has stopped is frozen ON THE DEVICE: its ``x`` keeps its bits however long the others run, so the result
@@ -1491,12 +1698,15 @@ class ReciprocalSensitivity(Sensitivity):
 
         info: ``iterations`` (K,), ``relative_residual`` (K,) ``|r_k| / |b_k|`` of the recurrence, ``state`` (K,) -- 0
         stopped by ``maxit``, 1 converged, 2 breakdown (``<p, (H + lambda R) p> <= 0``), 3 a sum was not finite --,
-        ``history`` (list of (K,) relative residuals, one per look at the table, the one after the set-up first) and
-        ``hessian_passes``.
+        ``history`` (list of (K,) relative residuals, one per look at the table, the one after the set-up first),
+        ``hessian_passes`` (``H p`` passes only), ``preconditioner_passes`` (application passes of ``'data'``, one more
+        than the former for the set-up; otherwise 0) and ``data_rank`` (the rank used; otherwise ``None``); with
+        ``'data'`` also ``setup_seconds`` of the preconditioner: gram / download / eigh / upload.
 
         The weights are uploaded once and one set of scratch buffers serves all passes. ``keep='host'``: every pass
         uploads the two stacks of every frequency again, as every block product does -- ``kept_bytes`` over PCIe per
-        iteration; ``keep='device'`` is the mode this method is meant for. No solve: ``n_solves`` does not move."""
+        iteration, and an application pass of ``'data'`` uploads them twice, once for each of its halves;
+        ``keep='device'`` is the mode this method is meant for. No solve: ``n_solves`` does not move."""
         import torch
         from emg3d_amd import _lib
         from emg3d_amd._device import _ptr, _stream
@@ -1511,7 +1721,11 @@ class ReciprocalSensitivity(Sensitivity):
         w = self._check_weights(weights)
         K = len(lam)
         on_dev, single, b = self._check_rhs(rhs, K)
-        if precondition:
+        by_data = isinstance(precondition, str) and precondition == 'data'
+        if by_data:
+            data_rank = self._check_data_rank(data_rank)
+            self._require_data_preconditioner()
+        elif precondition:
             self._require_model_grid('gauss_newton_solve(precondition=True)', 'before the modulus is taken')
         dev = self._device()
         self.forward()
@@ -1523,19 +1737,12 @@ class ReciprocalSensitivity(Sensitivity):
         x, p = torch.zeros_like(r), torch.zeros_like(r)
         geo = self._regulariser_geometry(mask, dev)
         nx, ny, nz, hx, hy, hz, dmask = geo
-        hd = rd = None
-        if precondition:
+        hd = rd = pre = None
+        if by_data:
+            pre = self._data_preconditioner_setup(dev, w, self._regulariser_diagonal(geo, alphas, irls, dev), dmask, data_rank)
+        elif precondition:
             hd = self._hessian_diagonal_block(w, dev)[0].contiguous()
-            if irls is None:
-                rd = torch.empty(ncell, dtype=torch.float64, device=dev)
-                _lib.check(L.emg3d_dev_model_regulariser_diagonal(
-                    nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, None if dmask is None else _ptr(dmask), _ptr(rd),
-                    _stream()), 'emg3d_dev_model_regulariser_diagonal')
-            else:                                                   # one diagonal of R per component
-                rd = torch.empty((n, ncell), dtype=torch.float64, device=dev)
-                _lib.check(L.emg3d_dev_model_regulariser_weighted_diagonal(
-                    nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *alphas, None if dmask is None else _ptr(dmask),
-                    *self._irls_args(irls, ncell), n, _ptr(rd), _stream()), 'emg3d_dev_model_regulariser_weighted_diagonal')
+            rd = self._regulariser_diagonal(geo, alphas, irls, dev)
         host = np.zeros((K, L.emg3d_pcg_table_len(K) // K))     # lambda, <b,b>, <r,z> new / old, <p,q>, <r,r>, iterations, state
         host[:, 0] = lam
         table = torch.from_numpy(host).to(dev)
@@ -1555,7 +1762,19 @@ class ReciprocalSensitivity(Sensitivity):
             _lib.check(L.emg3d_dev_pcg_direction_rd(ncell, n, K, first, _ptr(p), _ptr(r), opt[0], opt[1], ncell, opt[2],
                                                     _ptr(table), _stream()), 'emg3d_dev_pcg_direction_rd')
 
+        def step_data(first, q=None):
+            # x, r as without a preconditioner (the sums of that kernel are overwritten by pcg_finish); z = M r stored
+            _lib.check(L.emg3d_dev_pcg_update(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), None if q is None else _ptr(q),
+                                              *opt, _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_update')
+            self._apply_data_preconditioner(pre, dev, kc, first, r, u, z, dmask, pq, ws, reuse)
+            _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, float(tol), _ptr(table), _ptr(pq), _ptr(ws), ws_len,
+                                              _stream()), 'emg3d_dev_pcg_scalar')
+            _lib.check(L.emg3d_dev_pcg_direction_z(ncell, n, K, first, _ptr(p), _ptr(z), _ptr(table), _stream()),
+                       'emg3d_dev_pcg_direction_z')
+
         def step(first, q=None):
+            if by_data:
+                return step_data(first, q)
             if irls is not None:
                 return step_rd(first, q)
             _lib.check(L.emg3d_dev_pcg_update(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), None if q is None else _ptr(q),
@@ -1572,6 +1791,9 @@ class ReciprocalSensitivity(Sensitivity):
             history.append(rel)
             return t, rel
         history, passes, reuse = [], 0, {}
+        if by_data:
+            pre['table'] = table
+            u, z = torch.zeros_like(r), torch.zeros_like(r)
         step(1)
         t, rel = look()
         for it in range(1, maxit + 1):
@@ -1584,7 +1806,10 @@ class ReciprocalSensitivity(Sensitivity):
             if it % check_every == 0 or it == maxit:
                 t, rel = look()
         info = {'iterations': t[:, 6].astype(int), 'relative_residual': rel, 'state': t[:, 7].astype(int),
-                'history': history, 'hessian_passes': passes}
+                'history': history, 'hessian_passes': passes, 'preconditioner_passes': passes + 1 if by_data else 0,
+                'data_rank': pre['rank'] if by_data else None}
+        if by_data:
+            info['setup_seconds'] = pre['seconds']
         return (x if (on_dev if on_device is None else on_device) else self.from_device(x)), info
 
     # ------------------------------------------------------- data-space normal matrix ---
@@ -1659,21 +1884,27 @@ class ReciprocalSensitivity(Sensitivity):
         ``keep='host'`` holds a second staging pair for the duration of the call when there is more than one
         frequency. Every computational grid must be the model grid."""
         import torch
-        from emg3d_amd import _lib
-        from emg3d_amd._device import _ptr, _stream
         m = self._check_model_weights(model_weights)            # raises before any GPU work
         self._require_model_grid('data_gram', 'before the product is taken')
         c = self._data_rows()
         dev = self._device()
         self.forward()
+        d = self._chain_factors(dev)
+        mw = (torch.from_numpy(np.ascontiguousarray(m)).to(dev).permute(0, 3, 2, 1).reshape(len(m), -1) * (d * d)).contiguous()
+        return self._data_gram_block(mw, c, dev).cpu().numpy()
+
+    def _data_gram_block(self, mw, c, dev):
+        """``data_gram`` on the device: ``mw`` holds the model weights times the squared chain factors, contiguous
+        float64 (n, n_cells) in HBM; ``c`` = ``_data_rows()``. Returns the matrix (M, M) in HBM."""
+        import torch
+        from emg3d_amd import _lib
+        from emg3d_amd._device import _ptr, _stream
         L = _lib.lib()
         rx, ry, rz = _EXPAND[self.model.case]
         ncell = self.model.grid.n_cells
         nx, ny, nz = self.model.grid.shape_cells
         nrec = len(self._rec[0])
         n = len(self.pairs) * nrec
-        d = self._chain_factors(dev)
-        mw = (torch.from_numpy(np.ascontiguousarray(m)).to(dev).permute(0, 3, 2, 1).reshape(len(m), -1) * (d * d)).contiguous()
         G = torch.zeros((c * n, c * n), dtype=torch.float64, device=dev)
         per_freq = list(self._per_frequency())
         # rows of G of a frequency's block: Re of its data (its pairs in the order of its stack), then Im
@@ -1710,7 +1941,7 @@ class ReciprocalSensitivity(Sensitivity):
                     del ws, blk
         finally:
             del second
-        return G.cpu().numpy()
+        return G
 
 
 def jvec(model, vector, sources, frequencies, receivers, **kwargs):

@@ -680,6 +680,39 @@ int emg3d_dev_pcg_update_rd(size_t n_cells, int vec_per_col, int ncol, int first
 int emg3d_dev_pcg_direction_rd(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *r,
                                const double *hdiag, const double *rdiag, size_t rdiag_stride,
                                const unsigned char *mask, const double *table, void *stream);
+/* The data-space (Woodbury) preconditioner of the block PCG above: with dinv = 1 / diag R (1 where
+ * that is not positive, 0 on inactive cells; vec_per_col rows dinv_stride doubles apart, stride 0: one row for all
+ * components), s = sqrt(data weights) and the eigenpairs (Q, L) of diag(s) J^ diag(dinv) J^T diag(s), per running column
+ *   u = dinv o r / lambda,   y = diag(s) Q diag(lambda / (lambda + L)) Q^T diag(s) (J^ u),   z = u - dinv o (J^T y) / lambda
+ * is z = (lambda diag R + J^T diag(s) Q Q^T diag(s) J^)^-1 r exactly, for every number of eigenpairs kept. J^ u and
+ * J^T y are a block pass over the kept fields (emg3d_dev_sensitivity_dots_block / _combine_block); the entries below
+ * are the rest. All fp64, no floating-point atomics, every sum in an order fixed by the sizes: same call, same bits.
+ * A column runs if its state [7] is 0 and (first != 0 or pq[col] in (0, inf]), as for emg3d_dev_pcg_update; the
+ * vector entries leave every element of another column as it is.
+ *
+ * emg3d_dev_pcg_scale: u = dinv o r / [0] per running column.
+ * emg3d_dev_data_space_filter: y (ncol x n_data) from d (ncol x n_data), both device, rows contiguous. q: n_data x rank
+ * doubles, row-major (the eigenvector of eigenvalues[j] >= 0 is column j), rank <= n_data; s: n_data. Two launches per
+ * eight columns, t = diag(phi) Q^T (s o d) into ws (emg3d_data_space_filter_ws_len doubles) and y = s o (Q t): Q is
+ * read once per stage for eight columns. A column whose state is not 0 gets y = 0, written.
+ * emg3d_dev_pcg_finish: z = u - dinv o g / [0] per running column, 0 where mask is 0, and the partial sums of <r, z>
+ * and <r, r> into ws in the layout of emg3d_dev_pcg_update (emg3d_pcg_ws_len doubles): emg3d_dev_pcg_scalar follows
+ * unchanged. Columns that do not run contribute zeros there, which emg3d_dev_pcg_scalar does not read.
+ * emg3d_dev_pcg_direction_z, per column of state 0: p = z + ([2] / [3]) p from the stored z (first: p = z).
+ * EMG3D_ERR_BADARG, nothing launched: sizes < 1, ncol > 65535 (vector entries), rank > n_data, a NULL or aliased
+ * vector, a stride that is neither 0 nor >= n_cells, pq NULL with first == 0; EMG3D_ERR_SCRATCH: ws too small. */
+int emg3d_dev_pcg_scale(size_t n_cells, int vec_per_col, int ncol, int first, double *u, const double *r,
+                        const double *dinv, size_t dinv_stride, const double *table, const double *pq, void *stream);
+size_t emg3d_data_space_filter_ws_len(int rank, int ncol);
+int emg3d_dev_data_space_filter(int n_data, int rank, int ncol, const double *q, const double *eigenvalues,
+                                const double *s, const double *d, double *y, const double *table, double *ws,
+                                size_t ws_len, void *stream);
+int emg3d_dev_pcg_finish(size_t n_cells, int vec_per_col, int ncol, int first, double *z, const double *u,
+                         const double *g, const double *r, const double *dinv, size_t dinv_stride,
+                         const unsigned char *mask, const double *table, const double *pq, double *ws, size_t ws_len,
+                         void *stream);
+int emg3d_dev_pcg_direction_z(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *z,
+                              const double *table, void *stream);
 
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid

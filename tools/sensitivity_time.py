@@ -30,9 +30,14 @@ regulariser -- what a user can write without the method --, the two taking turns
 profiles/gauss_newton_solve_times.txt. Then, for 'double', the weighted / sparse-norm regulariser: its
 kernel with weights only, norms of 1 and general norms beside the plain kernel and a copy of its bytes, and an iteration of
 ``gauss_newton_solve`` weighted against plain. Writes profiles/weighted_regulariser_times.txt.
+Leg ``gndata``: the data-space (Woodbury) preconditioner of ``gauss_newton_solve`` beside Jacobi, K = 1, 4,
+8: the application pass beside the Hessian pass, its vector kernels and the filter beside a copy of their bytes, an
+iteration of either route, the set-up by its steps, and iterations and wall time to ``tol = 1e-3`` at three dampings, the
+two routes taking turns for five rounds. Writes profiles/data_preconditioner_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
-                                     [--leg all|products|hessian|gram|single|block|gnsolve] [--field-dtype double|single]
+                                     [--leg all|products|hessian|gram|single|block|gnsolve|gndata]
+                                     [--field-dtype double|single]
                                      [--out profiles/sensitivity_times.txt]
                                      [--hessian-out profiles/hessian_diagonal_times.txt]
                                      [--gram-out profiles/data_gram_times.txt]
@@ -40,6 +45,7 @@ kernel with weights only, norms of 1 and general norms beside the plain kernel a
                                      [--block-out profiles/block_products_times.txt]
                                      [--gnsolve-out profiles/gauss_newton_solve_times.txt]
                                      [--weighted-out profiles/weighted_regulariser_times.txt]
+                                     [--gndata-out profiles/data_preconditioner_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -818,20 +824,165 @@ def weighted_block(rec, say, launches):
         del b, p, q
 
 
+GD_FACTORS = (1e-2, 1.0, 1e2)                # dampings of the solves to tol, times tr H / tr R
+GD_MAXIT = 400
+
+
+def data_preconditioner_block(rec, say, launches):
+    """The data-space preconditioner beside Jacobi on the kept fields of ``rec``: the application pass
+    beside the Hessian pass, the three vector kernels and the filter beside a device copy of their bytes, an iteration
+    of either route as the difference of runs of 2 x and 1 x ``GN_ITERATIONS`` iterations (the set-up drops out), the
+    set-up by its steps, and iterations and wall time to ``tol = 1e-3`` at three dampings -- the two routes taking turns."""
+    from emg3d_amd import _lib
+    from emg3d_amd._device import _ptr, _stream
+    L = _lib.lib()
+    grid = rec.model.grid
+    n, ncell = gradient._NCOMP[rec.model.case], grid.n_cells
+    dev = torch.device('cuda', torch.cuda.current_device())
+    w = rec._check_weights(None)
+    geo = rec._regulariser_geometry(None, dev)
+    hd = rec._hessian_diagonal_block(w, dev)[0].contiguous()
+    rd = rec._regulariser_diagonal(geo, GN_REG, None, dev)
+    lam0 = float(hd.sum() / (n * rd.sum()))
+    reg = dict(smallness=GN_REG[0], smoothness=GN_REG[1:])
+
+    def timed(fn, count):
+        ms = []
+        for i in range(count + 2):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= 2:
+                ms.append(a.elapsed_time(b))
+        return float(np.median(ms)), float(min(ms)), float(max(ms) - min(ms))
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), out
+    rng = np.random.default_rng(2)
+    for K in GN_K:
+        lam = lam0 * 10.0 ** np.linspace(-1, 1, K)
+        b = rec.to_device(rng.standard_normal((K, n) + tuple(grid.shape_cells)))
+        pre = rec._data_preconditioner_setup(dev, w, rd, None, None)
+        M, rank = pre['n_data'], pre['rank']
+        host = np.zeros((K, 8))
+        host[:, 0] = lam
+        host[:, 2], host[:, 3] = 1.0, 2.0
+        pre['table'] = table = torch.from_numpy(host).to(dev)
+        ws_len = L.emg3d_pcg_ws_len(ncell, K)
+        ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
+        pq = torch.ones(K, dtype=torch.float64, device=dev)
+        r, p = b.clone(), b.clone()
+        u, z, g = (torch.zeros_like(b) for _ in range(3))
+        reuse = {}
+
+        def k_hessian():
+            rec._gradient_block(rec._block_products(dev, 8, block=p, weights=w, reuse=reuse)[1])
+
+        def k_apply():
+            rec._gradient_block(rec._block_products(dev, 8, block=u, reuse=reuse, apply=pre)[1])
+
+        def k_scale():
+            _lib.check(L.emg3d_dev_pcg_scale(ncell, n, K, 0, _ptr(u), _ptr(r), _ptr(pre['dinv']), 0, _ptr(table), _ptr(pq),
+                                             _stream()), 'emg3d_dev_pcg_scale')
+
+        def k_finish():
+            _lib.check(L.emg3d_dev_pcg_finish(ncell, n, K, 0, _ptr(z), _ptr(u), _ptr(g), _ptr(r), _ptr(pre['dinv']), 0, None,
+                                              _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_finish')
+
+        def k_direction():
+            _lib.check(L.emg3d_dev_pcg_direction_z(ncell, n, K, 0, _ptr(p), _ptr(z), _ptr(table), _stream()),
+                       'emg3d_dev_pcg_direction_z')
+        d, y = torch.randn((K, M), dtype=torch.float64, device=dev), torch.zeros((K, M), dtype=torch.float64, device=dev)
+        fws_len = L.emg3d_data_space_filter_ws_len(rank, K)
+        fws = torch.empty(fws_len, dtype=torch.float64, device=dev)
+
+        def k_filter():
+            _lib.check(L.emg3d_dev_data_space_filter(M, rank, K, _ptr(pre['q']), _ptr(pre['eigenvalues']), _ptr(pre['s']),
+                                                     _ptr(d), _ptr(y), _ptr(table), _ptr(fws), fws_len, _stream()),
+                       'emg3d_dev_data_space_filter')
+        k_scale(), k_hessian(), k_apply()
+        for _ in range(2):                                       # the two passes taking turns
+            hm, hb, hs = timed(k_hessian, launches)
+            am, ab, asp = timed(k_apply, launches)
+            say(f"  K = {K}: Hessian pass median {hm:7.3f} ms (fastest {hb:7.3f}, spread {hs:6.3f}); application pass median "
+                f"{am:7.3f} ms (fastest {ab:7.3f}, spread {asp:6.3f}); ratio of the medians {am / hm:4.2f}")
+        elems = K * n * ncell
+        for name, fn, nbytes in (('scale', k_scale, elems * 16 + ncell * 8), ('finish', k_finish, elems * 32 + ncell * 8),
+                                 ('direction_z', k_direction, elems * 24)):
+            src = torch.empty(nbytes // 16, dtype=torch.float64, device=dev)
+            dst = torch.empty_like(src)
+            med, best, _ = timed(fn, launches)
+            cmed, cbest, _ = timed(lambda: dst.copy_(src), launches)
+            say(f"  K = {K}: {name:12s} median {med:7.3f} ms (fastest {best:7.3f}), {nbytes / 1e6:8.1f} MB algorithmic = "
+                f"{nbytes / med / 1e9:5.2f} TB/s; copy that moves the same bytes {cmed:7.3f} ms (fastest {cbest:7.3f}); ratio to "
+                f"the copy rate {cmed / med:4.2f}")
+            del src, dst
+        p.copy_(b)
+        med, best, _ = timed(k_filter, launches)
+        src = torch.empty(max(2, M * rank), dtype=torch.float64, device=dev)
+        dst = torch.empty_like(src)
+        cmed, cbest, _ = timed(lambda: dst.copy_(src), launches)
+        say(f"  K = {K}: filter       median {med:7.3f} ms (fastest {best:7.3f}), M = {M}, rank {rank}, Q read twice = "
+            f"{2 * M * rank * 8 / 1e3:.1f} kB in {2 * -(-K // 8)} launches; a copy of those bytes {cmed:7.3f} ms (fastest "
+            f"{cbest:7.3f}): bound by launches, not by bytes")
+        del src, dst
+        say(f"  K = {K}: set-up of the preconditioner (ms): " +
+            ", ".join(f"{name} {1e3 * t:.2f}" for name, t in pre['seconds'].items()) + f"; M = {M}")
+
+        def run(route, its):
+            return rec.gauss_newton_solve(b, lam, tol=1e-30, maxit=its, check_every=GN_CHECK, precondition=route, **reg)
+        for route in (True, 'data'):
+            run(route, 2)                                        # warm-up
+        per = {True: [], 'data': []}
+        for _ in range(GN_ROUNDS):
+            for route in (True, 'data'):
+                t1, _ = wall(lambda: run(route, GN_ITERATIONS))
+                t2, (_, info) = wall(lambda: run(route, 2 * GN_ITERATIONS))
+                per[route].append((t2 - t1) / GN_ITERATIONS)
+        say(f"  K = {K}: per iteration (wall, (2 x {GN_ITERATIONS} - {GN_ITERATIONS}) iterations / {GN_ITERATIONS}), rounds: Jacobi "
+            f"{' '.join(f'{t:.3f}' for t in per[True])} ms (mean {np.mean(per[True]):.3f}); data "
+            f"{' '.join(f'{t:.3f}' for t in per['data'])} ms (mean {np.mean(per['data']):.3f}); ratio of the means "
+            f"{np.mean(per['data']) / np.mean(per[True]):.2f}")
+        del b, r, p, u, z, g, reuse, pre
+    # what users care about: iterations and wall time to tol 1e-3, one right-hand side, three dampings in one call
+    lam = lam0 * np.array(GD_FACTORS)
+    b = rec.to_device(rng.standard_normal((1, n) + tuple(grid.shape_cells)))[0]
+
+    def solve(route):
+        return rec.gauss_newton_solve(b, lam, tol=1e-3, maxit=GD_MAXIT, check_every=GN_CHECK, precondition=route, **reg)
+    for route in (True, 'data'):
+        rec.gauss_newton_solve(b, lam, tol=1e-3, maxit=2, precondition=route, **reg)
+    for _ in range(GN_ROUNDS):
+        for route in (True, 'data'):
+            t, (_, info) = wall(lambda: solve(route))
+            say(f"  to tol 1e-3, dampings {GD_FACTORS} x tr H / tr R ({lam0:.3e}), maxit {GD_MAXIT}: "
+                f"{'Jacobi' if route is True else 'data  '} iterations {info['iterations'].tolist()}, states "
+                f"{info['state'].tolist()}, relative residuals {[f'{v:.1e}' for v in info['relative_residual']]}, "
+                f"{info['hessian_passes']} + {info['preconditioner_passes']} passes, {t:.1f} ms with the set-up")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
-    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block', 'gnsolve'), default='all',
+    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block', 'gnsolve', 'gndata'),
+                    default='all',
                     help="products: the inner iteration four ways and its two reductions; hessian: hessian_diagonal against "
                          "the row-by-row route (needs only the set-up of ReciprocalSensitivity); gram: data_gram against the "
                          "route through jtvec, one frequency and two (the same set-up, once per survey); single: "
                          "field_dtype 'double' and 'single' side by side (not part of 'all'); block: K vectors per pass, the "
                          "block kernels and hessian_vec_block against K single calls (not part of 'all'); gnsolve: an "
                          "iteration of gauss_newton_solve, its kernels and the same iteration from torch operations (not "
-                         "part of 'all')")
+                         "part of 'all'); gndata: the data-space preconditioner of gauss_newton_solve beside Jacobi (not part "
+                         "of 'all')")
     ap.add_argument('--field-dtype', choices=('double', 'single'), default='double',
                     help="how ReciprocalSensitivity keeps its fields in the reciprocal, hessian and gram legs")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
@@ -841,6 +992,7 @@ def main():
     ap.add_argument('--block-out', default=os.path.join(ROOT, 'profiles', 'block_products_times.txt'))
     ap.add_argument('--gnsolve-out', default=os.path.join(ROOT, 'profiles', 'gauss_newton_solve_times.txt'))
     ap.add_argument('--weighted-out', default=os.path.join(ROOT, 'profiles', 'weighted_regulariser_times.txt'))
+    ap.add_argument('--gndata-out', default=os.path.join(ROOT, 'profiles', 'data_preconditioner_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -960,6 +1112,20 @@ def main():
             f.write('\n'.join(lines) + '\n')
         with open(args.weighted_out, 'w') as f:
             f.write('\n'.join(weighted) + '\n')
+        return
+    if args.leg == 'gndata':
+        lines[1] = (f"# {wl['label']}; {K} sources x 1 frequency, {len(recs)} receivers; (H + lambda_k R) x_k = b_k, the data-space "
+                    f"(Woodbury) preconditioner beside Jacobi, smallness {GN_REG[0]}, smoothness {GN_REG[1:]}, all weights one, "
+                    "field_dtype 'double'; times in ms")
+        rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
+                                             batch=K)
+        rec.forward()
+        say(f"{rec!r}")
+        data_preconditioner_block(rec, say, args.launches)
+        rec.release()
+        os.makedirs(os.path.dirname(os.path.abspath(args.gndata_out)), exist_ok=True)
+        with open(args.gndata_out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
         return
     if args.leg in ('hessian', 'gram'):
         rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
