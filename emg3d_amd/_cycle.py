@@ -212,7 +212,7 @@ def coarse_correction(clv, var, budget, first_level=1, graphed=None, top=None):
                 #  key would match again as soon as the options return to their old values)
                 root = top if top is not None else clv
                 _purge_stale_graphs(root, key[-1])
-                _drop_stale_point_factors(root)
+                _drop_stale_factors(root)
             entry = cache[key] = {'work': None, 'graph': None, 'seen': 0}
         if entry['seen'] < GRAPH_AFTER:
             before = var.smoother_cell_sweeps
@@ -247,18 +247,17 @@ def _purge_stale_graphs(lv, fingerprint, seen=None):
         _purge_stale_graphs(link['level'], fingerprint, seen)
 
 
-def _drop_stale_point_factors(lv, seen=None):
-    """The eta-sum buffers of the point smoother are kept per value of the option point_tile_min
-    (DeviceLevel.point_factors); once no graph of another option set is left, only the current value's are."""
+def _drop_stale_factors(lv, seen=None):
+    """The factor buffers whose format follows the options -- the eta sums of the point smoother, the line records
+    (fp64 or compact) -- are kept per format (DeviceLevel.point_factors / line_factors / _line_factor_slots); once no
+    graph of another option set is left, only those of the current options are."""
     seen = set() if seen is None else seen
     if id(lv) in seen:
         return
     seen.add(id(lv))
-    now = ('point', _lib.lib().emg3d_get_option(b'point_tile_min'))
-    for k in [k for k in lv._factors if isinstance(k, tuple) and k[0] == 'point' and k != now]:
-        del lv._factors[k]
+    lv.drop_stale_factors()
     for link in lv.children.values():
-        _drop_stale_point_factors(link['level'], seen)
+        _drop_stale_factors(link['level'], seen)
 
 
 # ------------------------------------------------------------------ termination ---------

@@ -215,6 +215,7 @@ class DeviceLevel:
         self._child_flags = (base | bits) if on else base
         self.flags = (base | _lib.LEVEL_LINE_COMPACT | (_lib.LEVEL_POINT_COMPACT if point_here else 0)) if on else base
         self._c.flags = self.flags
+        self._format_sig = None         # (the record formats follow the flags)
         self.work.line_compact = bool(on)
 
     def uses_line_compact(self, lines=True):
@@ -245,6 +246,53 @@ class DeviceLevel:
         return hit[1]
 
     # ------------------------------------------------------------------- kernels ------
+    def _line_format_signature(self):
+        """Bytes of the factor records of the three line directions as set-up and launcher lay them out under the
+        CURRENT options (emg3d_line_fac_bytes_lv: fp64 T + N records, or compact T records -- the two never have the
+        same size): what factor buffers are keyed on. Asked again only when an option has changed."""
+        return self._formats()[1]
+
+    def _formats(self):
+        lib = _lib.lib()
+        gen = lib.emg3d_options_generation()
+        hit = self.__dict__.get('_format_sig')
+        if hit is None or hit[0] != gen:
+            point = ('point', lib.emg3d_get_option(b'point_tile_min'), int(lib.emg3d_point_compact_used(self._cref)),
+                     int(lib.emg3d_point_fac_bytes_lv(self._cref)))
+            hit = self._format_sig = (gen, tuple(int(lib.emg3d_line_fac_bytes_lv(self._cref, d)) for d in (1, 2, 3)),
+                                      point)
+        return hit
+
+    def _line_format(self, lr):
+        return self._formats()[1][lr - 1]
+
+    def _point_key(self):
+        """Key of the point smoother's eta-sum buffer: the option that selects the sweep schedule (and with it the
+        layout), whether the sums are single precision (option point_compact, level flag) and the bytes that gives.
+        Like the line formats it is asked again only when an option has changed."""
+        return self._formats()[2]
+
+    def drop_stale_factors(self):
+        """Free every factor buffer of this level whose format the current options do not use: parked ones, and
+        those still in place for a direction that has not been asked for since the options changed. Called once no
+        captured graph of another option set is left (``_cycle._drop_stale_factors``: such graphs hold the buffers'
+        addresses) -- so only from a graphed coarse-grid correction; a hierarchy that never captures keeps its parked
+        buffers, at most one set per format, for its lifetime."""
+        now = self._point_key()
+        for k in [k for k in self._factors if isinstance(k, tuple)]:
+            if (k[0] == 'point' and k != now) or (k[0] == 'line' and k[2] != self._line_format(k[1])):
+                del self._factors[k]
+        formats = self.__dict__.get('_line_formats', {})
+        for lr in [lr for lr in (1, 2, 3) if lr in self._factors and formats.get(lr, self._line_format(lr)) != self._line_format(lr)]:
+            del self._factors[lr], formats[lr]
+        sig = self._line_format_signature()
+        sets = self.__dict__.get('_slot_sets')
+        if sets:
+            for k in [k for k in sets if k != sig]:
+                del sets[k]
+        if self.__dict__.get('_slots') is not None and self._slot_sig != sig:
+            del self._slots         # (``_line_factor_slots`` un-parks or allocates the current signature's set)
+
     def _line_factor_slots(self, lr):
         """Policy 'rebuild': a level holds TWO factor buffers (the two directions of a line-relaxation
         code; 608 instead of 912 B per cell with all three directions in use; policy 'single': ONE buffer,
@@ -259,15 +307,31 @@ class DeviceLevel:
         lib = _lib.lib()
         work = self.work
         slots = self.__dict__.get('_slots')
+        # The record format of every direction (fp64 + N records, or compact) follows the OPTIONS as well as the level's
+        # flags (emg3d_line_compact_used: line_compact, and everything that selects the line kernel), and set-up and
+        # launcher decide it anew at every call: one set of buffers per format signature, sized for it. The set of another
+        # signature is parked, not freed -- graphs captured under the options it belongs to hold its addresses -- until
+        # those graphs go (``drop_stale_factors``); a parked set that comes back starts without factors.
+        sig = self._line_format_signature()
+        if slots is None or self._slot_sig != sig:
+            sets = self.__dict__.setdefault('_slot_sets', {})
+            if slots is not None:
+                sets[self._slot_sig] = slots
+            slots = self._slots = sets.pop(sig, None)
+            self._slot_sig = sig
+            for sl in slots or ():
+                sl['dir'] = None
         if slots is None:
             nx, ny, nz = self.grid.shape_cells
-            nf = max(lib.emg3d_line_fac_bytes_lv(self._cref, d) for d in (1, 2, 3))      # (compact records: smaller)
+            nf = max(sig)                                                                # (compact records: smaller)
             nl = max(lib.emg3d_line_lfac_bytes(d, nx, ny, nz) for d in (1, 2, 3))
             slots = self._slots = [{'dir': None, 'used': 0,
                                     'fac': torch.empty(nf, dtype=torch.uint8, device=self.device),
                                     'lfac': torch.empty(nl, dtype=torch.uint8, device=self.device)}
                                    for _ in range(1 if work.factor_policy == 'single' else 2)]
-            self._slot_epoch, self._slot_clock, self.factor_rebuilds = work.factor_epoch, 0, 0
+            self._slot_sig = sig
+            self._slot_epoch, self._slot_clock = work.factor_epoch, self.__dict__.get('_slot_clock', 0)
+            self.factor_rebuilds = self.__dict__.get('factor_rebuilds', 0)
         if not self.__dict__.get('is_top', False) and self._slot_epoch != work.factor_epoch:
             for sl in slots:
                 sl['dir'] = None
@@ -299,6 +363,19 @@ class DeviceLevel:
         hierarchy's policy 'rebuild', held in one of two buffers per level (``_line_factor_slots``)."""
         if self.work.factor_policy in ('rebuild', 'single'):
             return self._line_factor_slots(lr)
+        # The format of the records is decided by set-up and launcher at every call, from the level's flags AND the
+        # options (emg3d_line_compact_used): the buffers under `lr` are those of the format noted in `_line_formats`.
+        # When the options have moved it, the buffers are parked under ('line', lr, format) -- graphs captured under
+        # the earlier options hold their addresses -- and come back with it, or go with those graphs
+        # (``drop_stale_factors``).
+        fmt = self._line_format(lr)
+        formats = self.__dict__.setdefault('_line_formats', {})
+        if lr in self._factors and formats.get(lr, fmt) != fmt:
+            self._factors[('line', lr, formats[lr])] = self._factors.pop(lr)
+            parked = self._factors.pop(('line', lr, fmt), None)
+            if parked is not None:
+                self._factors[lr] = parked
+        formats[lr] = fmt
         if lr not in self._factors:
             lib = _lib.lib()
             nx, ny, nz = self.grid.shape_cells
@@ -314,11 +391,12 @@ class DeviceLevel:
 
     def point_factors(self):
         """Eta edge sums of the point smoother (emg3d_dev_point_setup), built on first use. Their
-        layout follows the sweep schedule of the level (option point_tile_min): one buffer per value
-        of that option, all kept -- graphs captured under an earlier value (``_cycle.coarse_correction``
+        layout follows the sweep schedule of the level (option point_tile_min) and their precision the option
+        point_compact and the level's flags, both read by set-up and launcher at every call: one buffer per
+        ``_point_key``, all kept -- graphs captured under an earlier one (``_cycle.coarse_correction``
         keys them on the option set) still hold its buffer's address."""
         lib = _lib.lib()
-        key = ('point', lib.emg3d_get_option(b'point_tile_min'))
+        key = self._point_key()
         if key not in self._factors:
             fac = torch.empty(lib.emg3d_point_fac_bytes_lv(self._cref), dtype=torch.uint8, device=self.device)
             _lib.check(lib.emg3d_dev_point_setup(self._cref, _ptr(fac), _stream()),

@@ -17,7 +17,7 @@ import torch
 
 import emg3d_amd as emg3d
 from emg3d_amd import core, solver, _lib
-from emg3d_amd._device import DeviceLevel
+from emg3d_amd._device import DeviceLevel, _stream
 from oracle import core as ocore
 from oracle import mg_ref
 from helpers import (admissible_sc_dirs, coarse_grid, pec_mask, random_field, random_level, relerr, sc_factors,
@@ -3051,6 +3051,7 @@ def test_device_restrict_and_prolong_vs_oracle_single_and_batched(shape, case, e
 
     * every source's coarse source equals mg_ref.restriction of ITS residual (1e-14), the coarse field, filled with a
       sentinel before, is exactly zero, and the batched call gives each source the bits of its own batch-1 call;
+      emg3d_dev_restrict_batch (the entry without the clear) gives the same bits and leaves the coarse field alone;
     * every source's fine field after `+=` equals mg_ref.prolongation (1e-14), its PEC edges keep their bits, the
       coarse field is untouched, and batched equals single bit for bit."""
     grid, vm, rng = random_level(shape, case, dtype, sum(shape) + 1, extras=extras, stretch=1.03)
@@ -3091,6 +3092,17 @@ def test_device_restrict_and_prolong_vs_oracle_single_and_batched(shape, case, e
                         single_cs[b] = cs[k].copy()
                     else:
                         assert np.array_equal(cs[k], single_cs[b]), (at, b)
+                # the entry without the clear (emg3d_dev_restrict_batch), same weights: the bits of the coarse source
+                # above, and a coarse field that keeps every bit of the sentinel
+                c.s.fill_(_SENTINEL)
+                c.e.fill_(_SENTINEL)
+                _lib.check(_lib.lib().emg3d_dev_restrict_batch(
+                    *c.parts(c.s), *lv.parts(lv.r), *lv.child(sc_dir)['wptr'], *shape, sc_dir, int(dtype is complex),
+                    batch, n, nc, _stream()), 'emg3d_dev_restrict_batch')
+                assert np.array_equal(c.s.cpu().numpy().reshape(batch, nc), cs), at
+                kept = c.e.cpu().numpy()
+                assert np.array_equal(kept.view(np.uint64), np.full_like(kept, _SENTINEL).view(np.uint64)), at
+                assert np.array_equal(lv.r.cpu().numpy(), _stack(res, srcs).numpy()), at
                 # prolongation
                 c.e.copy_(_stack(ces, srcs))
                 lv.e.copy_(_stack(fines, srcs))
