@@ -45,6 +45,11 @@ def zero(t):
     _lib.check(_lib.lib().emg3d_dev_zero(_ptr(t), t.numel() * t.element_size(), _stream()), 'emg3d_dev_zero')
 
 
+def free_hbm(dev):
+    """Bytes of HBM that an allocation may still take: what the device reports free plus the allocator's reserve."""
+    return torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+
+
 def coarsen_flags(sc_dir):
     """(cx, cy, cz): is the direction coarsened for this sc_dir? (solver.py:891-897)"""
     return (sc_dir not in (1, 5, 6), sc_dir not in (2, 4, 6), sc_dir not in (3, 4, 5))

@@ -691,14 +691,14 @@ class ReciprocalSensitivity(Sensitivity):
         a view of a (rows, stride) allocation whose rows start on 16-byte boundaries (full-width loads in
         ``emg3d_dev_sensitivity_dots_sp`` / ``_combine_sp``)."""
         import torch
+        from emg3d_amd._device import free_hbm
         if self.field_dtype == 'single':
             dtype = {torch.complex128: torch.complex64, torch.float64: torch.float32}[dtype]
         size = torch.empty(0, dtype=dtype).element_size()
         stride = n if self.field_dtype == 'double' else -(-n * size // 16) * 16 // size
         if self.keep == 'host':
             return torch.empty((rows, stride), dtype=dtype, pin_memory=True)[:, :n]
-        need = rows * stride * size
-        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        need, free = rows * stride * size, free_hbm(dev)
         if need > free:
             raise MemoryError(f"ReciprocalSensitivity: a stack of {rows} kept fields needs {need:,} B of HBM, "
                               f"{free:,} B are free; keep='host' holds the fields in pinned host memory instead.")
@@ -828,25 +828,25 @@ class ReciprocalSensitivity(Sensitivity):
 
     # ------------------------------------------------------------------------------- jvec ---
     def jvec(self, vector):
-        """As ``Sensitivity.jvec``, without a solve: a block of one column through ``_block_products`` -- per frequency
+        """As ``Sensitivity.jvec``, without a solve: a block of one column through a ``_BlockPass`` -- per frequency
         one ``emg3d_dev_edge_weights`` and one ``emg3d_dev_sensitivity_dots_block``, which runs the single-vector kernel
         for one column."""
         v = _check_vector(self.model, vector)                   # raises on a wrong shape, before any GPU work
         dev = self._device()
         self.forward()
-        jv = self._data_of(self._block_products(dev, 1, block=self._upload_block(v[None], dev))[0])
+        jv = self._data_of(self._pass(dev, 1, 1).jvec(self._upload_block(v[None], dev)))
         return {pair: rows[0] for pair, rows in jv.items()}
 
     # ------------------------------------------------------------------------------ jtvec ---
     def jtvec(self, vector):
-        """As ``Sensitivity.jtvec``, without a solve: one data set through ``_block_products`` -- per frequency one
+        """As ``Sensitivity.jtvec``, without a solve: one data set through a ``_BlockPass`` -- per frequency one
         ``emg3d_dev_sensitivity_combine_block``, which runs the single-vector kernel for one column, with the
         coefficients ``conj(vector)`` (0 for NaN or a missing pair) and one ``emg3d_dev_edges_to_cells``; the anisotropy
         bookkeeping and the derivative chain on the device, only the model's own components cross to the host."""
         self._check_data(vector)
         dev = self._device()
         self.forward()
-        return self.from_device(self._gradient_block(self._block_products(dev, 1, data=[vector])[1]))[0]
+        return self.from_device(self._gradient_block(self._pass(dev, 1, 1).jtvec([vector])))[0]
 
     def misfit_and_gradient(self, observed, weights=None):
         """Misfit ``sum w |synthetic - observed|^2 / 2`` from the kept responses and its gradient
@@ -888,9 +888,6 @@ class ReciprocalSensitivity(Sensitivity):
         >= 0, as for ``misfit_and_gradient`` (NaN or a missing pair: 0; ``None``: all ones). Without a solve: per
         frequency one ``emg3d_dev_hessian_diagonal`` over the kept fields (a frequency whose weights are all zero is
         skipped). Every computational grid must be the model grid."""
-        import torch
-        from emg3d_amd import _lib
-        from emg3d_amd._device import _ptr, _stream
         w = self._check_weights(weights)                        # raises before any GPU work
         self._require_model_grid('hessian_diagonal', 'before the modulus is taken')
         dev = self._device()
@@ -992,192 +989,12 @@ class ReciprocalSensitivity(Sensitivity):
         # (K, n_cells, n) in memory = component fastest, then x: the Fortran order of every (n, nx, ny, nz) slice
         return block.permute(0, 2, 1).contiguous().cpu().numpy().reshape((K,) + rev + (n,)).transpose(0, 4, 3, 2, 1)
 
-    def _block_scratch(self, rows, stride, dtype, dev, what):
-        """(rows, stride) of ``dtype`` in HBM for ``rows`` columns of a pass; raises if that much is not free."""
-        import torch
-        need = rows * stride * torch.empty(0, dtype=dtype).element_size()
-        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        if need > free:                                  # (one column, as for jvec / jtvec: nothing smaller to advise)
-            raise MemoryError(f"ReciprocalSensitivity: the {what} of {rows} columns per pass need {need:,} B of HBM, "
-                              f"{free:,} B are free" + ("; a smaller `columns_per_pass` needs less." if rows > 1 else "."))
-        return torch.empty((rows, stride), dtype=dtype, device=dev)
-
-    def _block_products(self, dev, kc, block=None, data=None, weights=None, reuse=None, apply=None):
-        """The engine of ``jvec`` and ``jtvec`` (a block of one column, ``kc`` = 1) and of the three block methods,
-        frequency by frequency with ONE ``_fields_of`` each. ``block``
-        (device block): ``emg3d_dev_edge_weights`` per column and one ``emg3d_dev_sensitivity_dots_block`` per group of
-        at most ``kc`` columns -> jv, dict frequency name -> device tensor (K, ns, nr). Then, with coefficients (K, ns,
-        nr) from ``data`` (list of K data dictionaries: ``conj``, 0 for NaN or a missing pair; columns without a datum
-        at a frequency are left out there, a frequency without any is skipped) or from ``weights`` (the checked
-        dict: ``conj(weights * jv)``, formed on the device): one ``emg3d_dev_sensitivity_combine_block`` per group and
-        ``emg3d_dev_edges_to_cells`` per column -> the cell gradient (K, 3, n_cells) on the device. Uploads (the weights of
-        all frequencies; ``keep='host'``: a frequency's stacks) and the look at the free HBM come before a frequency's
-        first kernel: between its ``dots_block`` and its ``combine_block`` the host queues torch operations on (K, ns,
-        nr) and waits for nothing. ``data``: the coefficients of a frequency are uploaded before its ``combine_block``.
-
-        ``reuse``: a dict that a caller of many passes of one shape (``gauss_newton_solve``) hands to every one of them:
-        the uploaded weights and every scratch buffer are made by the first pass, kept in it and used again by the later
-        ones (all passes run on one stream, in order), so that a pass uploads and allocates nothing of its own. The
-        kernels, their arguments and the results are those of a call without it.
-
-        ``apply`` (with ``block`` alone; the set-up of ``_data_preconditioner_setup`` plus the PCG ``'table'``): the
-        data-space half of the data preconditioner between the two halves of the pass, in another order -- ALL
-        frequencies' ``dots_block`` first, their results gathered into the stacked real block (K, M) of ``stack_data`` by
-        torch index operations on those small tensors, ONE ``emg3d_dev_data_space_filter`` on it, then all frequencies'
-        ``combine_block`` with the coefficients ``conj`` of the filtered block, scattered back on the device. With
-        ``reuse`` it uploads nothing and the host waits for nothing between the kernels. ``keep='host'`` uploads each
-        frequency's stacks TWICE per application, once for each half. Without ``apply`` the function does what it did."""
-        import torch
-        from emg3d_amd import _lib
-        from emg3d_amd._device import _ptr, _stream
-        L = _lib.lib()
-        nrec, ncell = len(self._rec[0]), self.model.grid.n_cells
-        expand = _EXPAND[self.model.case]
-        K = len(block) if block is not None else len(data)
-        kc = min(kc, K)
-        per_freq = list(self._per_frequency())
-        stride = max(f[3].n_edges for f in per_freq)
-        stride += stride & 1                             # rows of float64 on 16-byte boundaries
-        combine = data is not None or weights is not None or apply is not None
-        wbuf = tbufs = regridded = grad = None
-        keep = {} if reuse is None else reuse            # (a dict of this call alone: nothing outlives it)
-
-        def kept(key, make):
-            if key not in keep:
-                keep[key] = make()
-            return keep[key]
-        if block is not None:
-            wbuf = kept('wbuf', lambda: self._block_scratch(kc, stride, torch.float64, dev, 'edge weights'))
-            # the derivative chain of the mapping for the whole block: vector_k * d sigma / d property_k
-            on_model = block * self._chain_factors(dev)
-            regridded = {0: on_model}
-        wdevs = keep.get('wdevs', {})
-        if combine:
-            tbufs = kept('tbufs', dict)                  # field type -> (kc, stride) edge vectors
-            if 'grad' in keep:
-                grad = keep['grad'].zero_()
-            else:
-                grad = keep['grad'] = torch.zeros((K, 3, ncell), dtype=torch.float64, device=dev)
-            if weights is not None and 'wdevs' not in keep:
-                keep['wdevs'] = wdevs
-                # every frequency's weights go up BEFORE the first kernel (an upload from pageable memory waits for the
-                # stream): between dots_block and combine_block there are only torch operations on (K, ns, nr)
-                for fname, mine, *_ in per_freq:
-                    wf = np.stack([weights[self.pairs[i]] for i in mine])
-                    if wf.any():                         # (a frequency whose weights are all zero: as hessian_diagonal)
-                        wdevs[fname] = torch.from_numpy(np.ascontiguousarray(wf)).to(dev)
-        jv = {}
-
-        def stage(fname):
-            """A frequency's two stacks in HBM, whether they are complex, and the type of its edge vectors."""
-            estack, xstack = self._fields_of(fname)
-            is_complex = int(estack.is_complex())
-            ftype = torch.complex128 if is_complex else torch.float64
-            if combine and ftype not in tbufs:          # (before the kernels: the look at the free HBM is a host call)
-                tbufs[ftype] = self._block_scratch(kc, stride, ftype, dev, 'edge vectors')
-            return estack, xstack, is_complex, ftype
-
-        def dots_half(f, staged):
-            fname, mine, gkey, grid, vol, plan, smu0 = f
-            estack, xstack, is_complex, ftype = staged
-            nx, ny, nz = grid.shape_cells
-            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
-            ns, nr = len(estack), len(xstack)
-            if gkey not in regridded:        # linear volume average: the map whose adjoint is the way back
-                regridded[gkey] = torch.stack([torch.stack([plan.on_device(c, log=False) for c in col])
-                                               for col in on_model])
-            cells = regridded[gkey]
-            # unit residual at a receiver: point source of strength conj(1 / (-s mu0)), times -s mu0 as every source
-            # (residual_source_field) = kappa p_r; jvec = p_r^T A^-1 (-s mu0 w e_s) = -s mu0 / kappa sum w e_s x_r
-            kappa = np.conj(1.0 / -smu0) * -smu0
-            scale = complex(-smu0 / kappa)
-            ws_len = L.emg3d_sensitivity_dots_block_ws_len(ns, nr, kc, n)
-            ws = kept(('ws', fname), lambda: torch.empty(ws_len, dtype=torch.float64, device=dev))
-            res = kept(('res', fname), lambda: torch.empty((K, ns, nr), dtype=ftype, device=dev))
-            dots, name = self._entry('emg3d_dev_sensitivity_dots_block', estack)
-            for g0 in range(0, K, kc):
-                g1 = min(g0 + kc, K)
-                for j in range(g0, g1):
-                    vx, vy, vz = (cells[j, k] for k in expand)
-                    w = wbuf[j - g0]
-                    _lib.check(L.emg3d_dev_edge_weights(nx, ny, nz, _ptr(vol), _ptr(vx), _ptr(vy), _ptr(vz), _ptr(w),
-                                                        _ptr(w, o1), _ptr(w, o2), _stream()), 'emg3d_dev_edge_weights')
-                _lib.check(dots(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack), xstack.stride(0), nr,
-                                _ptr(wbuf), stride, g1 - g0, scale.real, scale.imag, _ptr(res, g0 * ns * nr), _ptr(ws),
-                                ws_len, _stream()), name)
-            return res
-
-        def combine_half(f, staged, cdev, active):
-            fname, mine, gkey, grid, vol, plan, smu0 = f
-            estack, xstack, is_complex, ftype = staged
-            nx, ny, nz = grid.shape_cells
-            n, o1, o2 = grid.n_edges, grid.n_edges_x, grid.n_edges_x + grid.n_edges_y
-            ns, nr = len(estack), len(xstack)
-            tbuf = tbufs[ftype]
-            combine_block, name = self._entry('emg3d_dev_sensitivity_combine_block', estack)
-            for g0 in range(0, len(active), kc):
-                cols = active[g0:g0 + kc]
-                # the coefficients of the group, contiguous (columns that are left out make gaps)
-                cg = cdev[cols[0]:cols[-1] + 1] if cols[-1] - cols[0] + 1 == len(cols) else cdev[cols].contiguous()
-                _lib.check(combine_block(n, is_complex, _ptr(estack), estack.stride(0), ns, _ptr(xstack), xstack.stride(0), nr,
-                                         _ptr(cg), len(cols), _ptr(tbuf), stride, _stream()), name)
-                for row, j in enumerate(cols):
-                    t = tbuf[row]
-
-                    def to_cells(gtarget, nc):
-                        _lib.check(L.emg3d_dev_edges_to_cells(
-                            nx, ny, nz, is_complex, _ptr(t), _ptr(t, o1), _ptr(t, o2), smu0.real, smu0.imag, _ptr(vol),
-                            _ptr(gtarget), _ptr(gtarget, nc), _ptr(gtarget, 2 * nc), _stream()), 'emg3d_dev_edges_to_cells')
-                    self._on_model_grid(plan, grid, grad[j], to_cells)
-
-        if apply is not None:
-            # J^ u of ALL frequencies, the filter once on the stacked (K, M) block, then J^T y of all frequencies
-            M, rank, index = apply['n_data'], apply['rank'], apply['index']
-            live = [f for f in per_freq if f[0] in index]       # (a frequency whose weights are all zero has s = 0)
-            d = kept('d', lambda: torch.zeros((K, M), dtype=torch.float64, device=dev))
-            y = kept('y', lambda: torch.zeros((K, M), dtype=torch.float64, device=dev))
-            fws_len = L.emg3d_data_space_filter_ws_len(rank, K)
-            fws = kept('fws', lambda: torch.empty(fws_len, dtype=torch.float64, device=dev))
-            for f in live:
-                jv[f[0]] = dots_half(f, stage(f[0]))
-                parts = torch.view_as_real(jv[f[0]]).reshape(K, -1, 2)
-                d.index_copy_(1, index[f[0]][0], parts[:, :, 0])
-                d.index_copy_(1, index[f[0]][1], parts[:, :, 1])
-            _lib.check(L.emg3d_dev_data_space_filter(
-                M, rank, K, _ptr(apply['q']), _ptr(apply['eigenvalues']), _ptr(apply['s']), _ptr(d), _ptr(y),
-                _ptr(apply['table']), _ptr(fws), fws_len, _stream()), 'emg3d_dev_data_space_filter')
-            for f in live:
-                re, im = index[f[0]]
-                cdev = torch.complex(y[:, re], -y[:, im]).reshape(jv[f[0]].shape)       # conj, as for `data`
-                combine_half(f, stage(f[0]), cdev, list(range(K)))
-            return jv, grad
-        for f in per_freq:
-            fname, mine = f[0], f[1]
-            if weights is not None and fname not in wdevs:
-                continue
-            coef = None
-            if data is not None:
-                coef = np.zeros((K, len(mine), nrec), dtype=complex)
-                for k, vector in enumerate(data):
-                    for row, i in enumerate(mine):
-                        y = vector.get(self.pairs[i])
-                        if y is not None:
-                            coef[k, row] = np.conj(np.nan_to_num(np.asarray(y, dtype=complex), nan=0.0))
-                active = [k for k in range(K) if coef[k].any()]
-                if not active:
-                    continue
-            staged = stage(fname)
-            if block is not None:
-                jv[fname] = dots_half(f, staged)
-            if not combine:
-                continue
-            if coef is not None:
-                cdev = torch.from_numpy(coef if staged[2] else np.ascontiguousarray(coef.real)).to(dev)
-            else:
-                cdev = torch.conj_physical(jv[fname] * wdevs[fname]).contiguous()
-                active = list(range(K))
-            combine_half(f, staged, cdev, active)
-        return jv, grad
+    def _pass(self, dev, K, kc, weights=None):
+        """A ``_BlockPass`` over the kept fields for K columns in groups of at most ``kc`` (``weights``: the checked data
+        weights of its Hessian products): the engine of ``jvec`` and ``jtvec`` (a block of one column) and of the block
+        methods, which use one for one product, and of ``gauss_newton_solve``, which keeps one for all its passes."""
+        from emg3d_amd._blockpass import _BlockPass
+        return _BlockPass(self, dev, K, kc, _EXPAND[self.model.case], weights)
 
     def _gradient_block(self, grad):
         """The bookkeeping of ``_finish_gradient``, the same operations in the same order, for the cell gradients (K, 3,
@@ -1225,7 +1042,7 @@ class ReciprocalSensitivity(Sensitivity):
         dev = self._device()
         self.forward()
         block = self._check_device_block(block, dev) if on_dev else self._upload_block(block, dev)
-        return self._data_of(self._block_products(dev, kc, block=block)[0])
+        return self._data_of(self._pass(dev, len(block), kc).jvec(block))
 
     def _check_data_block(self, data):
         if isinstance(data, dict) or not hasattr(data, '__len__') or len(data) < 1:
@@ -1251,7 +1068,7 @@ class ReciprocalSensitivity(Sensitivity):
         data = self._check_data_block(data)                     # raises before any GPU work
         dev = self._device()
         self.forward()
-        out = self._gradient_block(self._block_products(dev, kc, data=data)[1])
+        out = self._gradient_block(self._pass(dev, len(data), kc).jtvec(data))
         return out if on_device else self.from_device(out)
 
     def hessian_vec_block(self, vectors, weights=None, on_device=None, columns_per_pass=8):
@@ -1270,7 +1087,7 @@ class ReciprocalSensitivity(Sensitivity):
         dev = self._device()
         self.forward()
         block = self._check_device_block(block, dev) if on_dev else self._upload_block(block, dev)
-        out = self._gradient_block(self._block_products(dev, kc, block=block, weights=w)[1])
+        out = self._gradient_block(self._pass(dev, len(block), kc, w).hessian_vec(block))
         return out if (on_dev if on_device is None else on_device) else self.from_device(out)
 
     # ------------------------------------------- regulariser and the inner Gauss-Newton solve ---
@@ -1593,23 +1410,6 @@ class ReciprocalSensitivity(Sensitivity):
                 'index': index, 'n_data': M, 'rank': rank, 'q_host': q_host, 'eigenvalues_host': eig, 's_host': s,
                 'seconds': seconds}
 
-    def _apply_data_preconditioner(self, pre, dev, kc, first, r, u, z, dmask, pq, ws, reuse):
-        """``z = M r`` for the running columns of ``pre['table']``: ``emg3d_dev_pcg_scale`` (u), one application pass of
-        ``_block_products`` (g = J^T y), ``emg3d_dev_pcg_finish`` (z, and the partial sums of <r, z> and <r, r> in
-        ``ws`` for ``emg3d_dev_pcg_scalar``). All blocks (K, n, n_cells) on the device; queued, nothing is waited for."""
-        from emg3d_amd import _lib
-        from emg3d_amd._device import _ptr, _stream
-        L = _lib.lib()
-        K, n, ncell = r.shape
-        pqp = None if pq is None else _ptr(pq)
-        _lib.check(L.emg3d_dev_pcg_scale(ncell, n, K, first, _ptr(u), _ptr(r), _ptr(pre['dinv']), pre['dinv_stride'],
-                                         _ptr(pre['table']), pqp, _stream()), 'emg3d_dev_pcg_scale')
-        g = self._gradient_block(self._block_products(dev, kc, block=u, reuse=reuse, apply=pre)[1])
-        _lib.check(L.emg3d_dev_pcg_finish(ncell, n, K, first, _ptr(z), _ptr(u), _ptr(g), _ptr(r), _ptr(pre['dinv']),
-                                          pre['dinv_stride'], None if dmask is None else _ptr(dmask), _ptr(pre['table']),
-                                          pqp, _ptr(ws), ws.numel(), _stream()), 'emg3d_dev_pcg_finish')
-        return z
-
     def _data_preconditioner(self, dampings, weights=None, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None,
                              data_rank=None, columns_per_pass=8, *, cell_weights=None, norms=None, linearise_at=None,
                              irls_eps=None):
@@ -1618,7 +1418,6 @@ class ReciprocalSensitivity(Sensitivity):
         block[k]`` for the K = ``len(dampings)`` columns of a device block as a new device block, through the kernels
         and the pass of the solve."""
         import torch
-        from emg3d_amd import _lib
         kc = self._check_columns(columns_per_pass)
         lam = self._check_dampings(dampings)
         alphas = self._check_regulariser(smallness, smoothness)
@@ -1629,24 +1428,31 @@ class ReciprocalSensitivity(Sensitivity):
         self._require_data_preconditioner()
         dev = self._device()
         self.forward()
-        L = _lib.lib()
-        K, ncell = len(lam), self.model.grid.n_cells
-        geo = self._regulariser_geometry(mask, dev)
-        pre = self._data_preconditioner_setup(dev, w, self._regulariser_diagonal(geo, alphas, self._upload_irls(irls, dev), dev),
-                                              geo[6], data_rank)
-        host = np.zeros((K, L.emg3d_pcg_table_len(K) // K))
-        host[:, 0] = lam
-        pre['table'] = torch.from_numpy(host).to(dev)
-        ws = torch.empty(L.emg3d_pcg_ws_len(ncell, K), dtype=torch.float64, device=dev)
-        reuse = {}
+        K, n, ncell = len(lam), _NCOMP[self.model.case], self.model.grid.n_cells
+        pcg = self._pcg(dev, torch.zeros((K, n, ncell), dtype=torch.float64, device=dev), lam, kc, w,
+                        self._regulariser_geometry(mask, dev), alphas, self._upload_irls(irls, dev), 'data', data_rank)
 
         def apply(block):
             r = self._check_device_block(block, dev)
             if len(r) != K:
                 raise ValueError(f"the block must have K = len(dampings) = {K} columns. Provided: {len(r)}.")
-            return self._apply_data_preconditioner(pre, dev, kc, 1, r, torch.zeros_like(r), torch.zeros_like(r), geo[6], None,
-                                                   ws, reuse)
-        return pre, apply
+            pcg.r.copy_(r)
+            return pcg.precondition(1).clone()
+        return pcg.pre, apply
+
+    def _pcg(self, dev, r, lam, kc, w, geo, alphas, irls, precondition, data_rank=None, tol=0.0):
+        """The ``_BlockPCG`` of ``gauss_newton_solve`` for the device residual block ``r`` (K, n, n_cells) after the
+        set-up of its preconditioner -- ``precondition``: ``'data'``, True (Jacobi: the two diagonals) or False --, on a
+        new ``_BlockPass``: every buffer of the iteration is allocated here, behind the temporaries of the set-up.
+        (``tol`` is read by the scalar step alone.)"""
+        from emg3d_amd._blockpass import _BlockPCG
+        hd = rd = pre = None
+        if precondition == 'data':
+            pre = self._data_preconditioner_setup(dev, w, self._regulariser_diagonal(geo, alphas, irls, dev), geo[6], data_rank)
+        elif precondition:
+            hd = self._hessian_diagonal_block(w, dev)[0].contiguous()
+            rd = self._regulariser_diagonal(geo, alphas, irls, dev)
+        return _BlockPCG(self._pass(dev, len(lam), kc, w), lam, r, tol, geo[6], (hd, rd), irls is not None, pre)
 
     def gauss_newton_solve(self, rhs, dampings, weights=None, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None,
                            tol=1e-3, maxit=50, precondition=True, check_every=4, on_device=None, columns_per_pass=8, *,
@@ -1707,9 +1513,6 @@ class ReciprocalSensitivity(Sensitivity):
         uploads the two stacks of every frequency again, as every block product does -- ``kept_bytes`` over PCIe per
         iteration, and an application pass of ``'data'`` uploads them twice, once for each of its halves;
         ``keep='device'`` is the mode this method is meant for. No solve: ``n_solves`` does not move."""
-        import torch
-        from emg3d_amd import _lib
-        from emg3d_amd._device import _ptr, _stream
         kc = self._check_columns(columns_per_pass)              # everything is validated before any GPU work
         lam = self._check_dampings(dampings)
         alphas = self._check_regulariser(smallness, smoothness)
@@ -1729,88 +1532,37 @@ class ReciprocalSensitivity(Sensitivity):
             self._require_model_grid('gauss_newton_solve(precondition=True)', 'before the modulus is taken')
         dev = self._device()
         self.forward()
-        L = _lib.lib()
         n, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
         b = self._check_device_block(b, dev) if on_dev else self._upload_block(b, dev)
         irls = self._upload_irls(irls, dev)
-        r = (b.expand(K, n, ncell) if single else b).clone()    # the residual, updated in place
-        x, p = torch.zeros_like(r), torch.zeros_like(r)
         geo = self._regulariser_geometry(mask, dev)
-        nx, ny, nz, hx, hy, hz, dmask = geo
-        hd = rd = pre = None
-        if by_data:
-            pre = self._data_preconditioner_setup(dev, w, self._regulariser_diagonal(geo, alphas, irls, dev), dmask, data_rank)
-        elif precondition:
-            hd = self._hessian_diagonal_block(w, dev)[0].contiguous()
-            rd = self._regulariser_diagonal(geo, alphas, irls, dev)
-        host = np.zeros((K, L.emg3d_pcg_table_len(K) // K))     # lambda, <b,b>, <r,z> new / old, <p,q>, <r,r>, iterations, state
-        host[:, 0] = lam
-        table = torch.from_numpy(host).to(dev)
-        dlam = torch.from_numpy(lam).to(dev)
-        pq = torch.zeros(K, dtype=torch.float64, device=dev)
-        ws_len = L.emg3d_pcg_ws_len(ncell, K)
-        ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
-        rws = torch.empty(L.emg3d_model_regulariser_ws_len(nx, ny, nz, K * n, n), dtype=torch.float64, device=dev)
-        opt = [None if t is None else _ptr(t) for t in (hd, rd, dmask)]
-
-        def step_rd(first, q=None):
-            _lib.check(L.emg3d_dev_pcg_update_rd(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), None if q is None else _ptr(q),
-                                                 opt[0], opt[1], ncell, opt[2], _ptr(table), _ptr(pq), _ptr(ws), ws_len,
-                                                 _stream()), 'emg3d_dev_pcg_update_rd')
-            _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, float(tol), _ptr(table), _ptr(pq), _ptr(ws), ws_len,
-                                              _stream()), 'emg3d_dev_pcg_scalar')
-            _lib.check(L.emg3d_dev_pcg_direction_rd(ncell, n, K, first, _ptr(p), _ptr(r), opt[0], opt[1], ncell, opt[2],
-                                                    _ptr(table), _stream()), 'emg3d_dev_pcg_direction_rd')
-
-        def step_data(first, q=None):
-            # x, r as without a preconditioner (the sums of that kernel are overwritten by pcg_finish); z = M r stored
-            _lib.check(L.emg3d_dev_pcg_update(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), None if q is None else _ptr(q),
-                                              *opt, _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_update')
-            self._apply_data_preconditioner(pre, dev, kc, first, r, u, z, dmask, pq, ws, reuse)
-            _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, float(tol), _ptr(table), _ptr(pq), _ptr(ws), ws_len,
-                                              _stream()), 'emg3d_dev_pcg_scalar')
-            _lib.check(L.emg3d_dev_pcg_direction_z(ncell, n, K, first, _ptr(p), _ptr(z), _ptr(table), _stream()),
-                       'emg3d_dev_pcg_direction_z')
-
-        def step(first, q=None):
-            if by_data:
-                return step_data(first, q)
-            if irls is not None:
-                return step_rd(first, q)
-            _lib.check(L.emg3d_dev_pcg_update(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), None if q is None else _ptr(q),
-                                              *opt, _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_update')
-            _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, float(tol), _ptr(table), _ptr(pq), _ptr(ws), ws_len,
-                                              _stream()), 'emg3d_dev_pcg_scalar')
-            _lib.check(L.emg3d_dev_pcg_direction(ncell, n, K, first, _ptr(p), _ptr(r), *opt, _ptr(table), _stream()),
-                       'emg3d_dev_pcg_direction')
+        pcg = self._pcg(dev, (b.expand(K, n, ncell) if single else b).clone(), lam, kc, w, geo, alphas, irls,
+                        'data' if by_data else bool(precondition), data_rank, tol)
 
         def look():
-            t = table.cpu().numpy()
+            t = pcg.table.cpu().numpy()
             with np.errstate(invalid='ignore', divide='ignore'):
                 rel = np.where(t[:, 1] > 0, np.sqrt(t[:, 5] / t[:, 1]), 0.0)
             history.append(rel)
             return t, rel
-        history, passes, reuse = [], 0, {}
-        if by_data:
-            pre['table'] = table
-            u, z = torch.zeros_like(r), torch.zeros_like(r)
-        step(1)
+        history, passes = [], 0
+        pcg.step(1)
         t, rel = look()
         for it in range(1, maxit + 1):
             if not np.any(t[:, 7] == 0):
                 break
-            q = self._gradient_block(self._block_products(dev, kc, block=p, weights=w, reuse=reuse)[1])
+            q = self._gradient_block(pcg.ps.hessian_vec(pcg.p))
             passes += 1
-            self._regulariser(geo, alphas, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws, irls=irls)
-            step(0, q)
+            self._regulariser(geo, alphas, pcg.p, q, beta=1.0, lam=pcg.lam, pq=pcg.pq, ws=pcg.rws, irls=irls)
+            pcg.step(0, q)
             if it % check_every == 0 or it == maxit:
                 t, rel = look()
         info = {'iterations': t[:, 6].astype(int), 'relative_residual': rel, 'state': t[:, 7].astype(int),
                 'history': history, 'hessian_passes': passes, 'preconditioner_passes': passes + 1 if by_data else 0,
-                'data_rank': pre['rank'] if by_data else None}
+                'data_rank': pcg.pre['rank'] if by_data else None}
         if by_data:
-            info['setup_seconds'] = pre['seconds']
-        return (x if (on_dev if on_device is None else on_device) else self.from_device(x)), info
+            info['setup_seconds'] = pcg.pre['seconds']
+        return (pcg.x if (on_dev if on_device is None else on_device) else self.from_device(pcg.x)), info
 
     # ------------------------------------------------------- data-space normal matrix ---
     def _data_rows(self):

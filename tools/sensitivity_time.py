@@ -76,6 +76,32 @@ def commit():
         return 'unknown'
 
 
+def sync():
+    torch.cuda.synchronize()
+    return time.perf_counter()
+
+
+def timed(fn, count):
+    """Median, fastest and spread of ``count`` launches (ms, HIP events), after two warm-up launches."""
+    ms = []
+    for i in range(count + 2):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        if i >= 2:
+            ms.append(a.elapsed_time(b))
+    return float(np.median(ms)), float(min(ms)), float(max(ms) - min(ms))
+
+
+def wall(fn):
+    """(wall time of ``fn()`` in ms, synchronised; its result)."""
+    t0 = sync()
+    out = fn()
+    return 1e3 * (sync() - t0), out
+
+
 def kernel_block(rec, say, launches):
     """``emg3d_dev_sensitivity_dots`` and ``emg3d_dev_sensitivity_combine`` alone on the kept fields of ``rec``."""
     from emg3d_amd import _lib
@@ -143,10 +169,6 @@ def hessian_block(rec, say, repeat, launches):
     from emg3d_amd import _lib
     from emg3d_amd._device import _ptr, _stream
     nrec = len(rec._rec[0])
-
-    def sync():
-        torch.cuda.synchronize()
-        return time.perf_counter()
 
     def row_by_row():
         out, calls = 0.0, 0
@@ -227,10 +249,6 @@ def gram_block(rec, say, repeat, launches, kernel):
     from emg3d_amd._device import _ptr, _stream
     nrec, npairs = len(rec._rec[0]), len(rec.pairs)
     N = npairs * nrec
-
-    def sync():
-        torch.cuda.synchronize()
-        return time.perf_counter()
 
     def route():
         Jhat, calls = None, 0
@@ -329,10 +347,6 @@ def single_block(recs, say, repeat, launches, v, y):
     from emg3d_amd._device import _ptr, _stream
     L = _lib.lib()
     names = list(recs)
-
-    def sync():
-        torch.cuda.synchronize()
-        return time.perf_counter()
     for name, rec in recs.items():
         (E, X), = rec._stacks.values()
         say(f"{name:7s} kept_bytes {rec.kept_bytes:,} B ({len(E) + len(X)} fields of {E.shape[1]:,} edges, {E.dtype}, row stride "
@@ -534,10 +548,6 @@ def block_methods(rec, say, repeat, label):
     grid = rec.model.grid
     ncomp = gradient._NCOMP[rec.model.case]
     rng = np.random.default_rng(1)
-
-    def sync():
-        torch.cuda.synchronize()
-        return time.perf_counter()
     for K in BLOCK_K:
         V = rng.standard_normal((K, ncomp) + tuple(grid.shape_cells))
         B = rec.to_device(V)
@@ -566,9 +576,7 @@ GN_REG = (1e-6, 1.0, 1.0, 1.0)              # smallness, smoothness x / y / z
 def gnsolve_block(rec, say, launches):
     """One iteration of the block PCG two ways on the kept fields of ``rec``: with the kernels of csrc/regularise.h in
     the order ``gauss_newton_solve`` launches them, and with torch operations around ``hessian_vec_block``."""
-    from emg3d_amd import _lib
-    from emg3d_amd._device import _ptr, _stream
-    L = _lib.lib()
+    from emg3d_amd._blockpass import _BlockPCG
     grid = rec.model.grid
     n, ncell = gradient._NCOMP[rec.model.case], grid.n_cells
     nx, ny, nz = grid.shape_cells
@@ -577,9 +585,7 @@ def gnsolve_block(rec, say, launches):
     geo = rec._regulariser_geometry(None, dev)
     hx, hy, hz = geo[3:6]
     hd = rec._hessian_diagonal_block(w, dev)[0].contiguous()
-    rd = torch.empty(ncell, dtype=torch.float64, device=dev)
-    _lib.check(L.emg3d_dev_model_regulariser_diagonal(nx, ny, nz, _ptr(hx), _ptr(hy), _ptr(hz), *GN_REG, None, _ptr(rd),
-                                                      _stream()), 'emg3d_dev_model_regulariser_diagonal')
+    rd = rec._regulariser_diagonal(geo, GN_REG, None, dev)
     lam0 = float(hd.mean() / rd.mean())
     # the slicing regulariser of the torch route: its coefficients are made once, as a user would
     shape = (nz, ny, nx)
@@ -601,64 +607,36 @@ def gnsolve_block(rec, say, launches):
             out.narrow(dim, 1, m - 1).sub_(d)
         return out.view(v.shape[0], n, ncell)
 
-    def timed(fn, count):
-        """Median and fastest of ``count`` launches (ms, HIP events), after two warm-up launches."""
-        ms = []
-        for i in range(count + 2):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i >= 2:
-                ms.append(a.elapsed_time(b))
-        return float(np.median(ms)), float(min(ms))
     rng = np.random.default_rng(2)
     for K in GN_K:
         lam = lam0 * 10.0 ** np.linspace(-1, 1, K)
         b = rec.to_device(rng.standard_normal((K, n) + tuple(grid.shape_cells)))
-        host = np.zeros((K, 8))
-        host[:, 0] = lam
-        dlam = torch.from_numpy(lam).to(dev)
-        pq = torch.zeros(K, dtype=torch.float64, device=dev)
-        ws_len = L.emg3d_pcg_ws_len(ncell, K)
-        ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
-        rws = torch.empty(L.emg3d_model_regulariser_ws_len(nx, ny, nz, K * n, n), dtype=torch.float64, device=dev)
-        x, r, p, q = (torch.zeros_like(b) for _ in range(4))
-        table = torch.zeros((K, 8), dtype=torch.float64, device=dev)
-        reuse = {}
+        ps = rec._pass(dev, K, 8, w)                       # the pass and the step pieces of gauss_newton_solve, tol 1e-30
+        pcg = _BlockPCG(ps, lam, b.clone(), 1e-30, None, (hd, rd))
+        host, q = pcg.table.cpu(), torch.zeros_like(b)
 
         def k_reg():
-            rec._regulariser(geo, GN_REG, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws)
-
-        def k_update(first=0):
-            _lib.check(L.emg3d_dev_pcg_update(ncell, n, K, first, _ptr(x), _ptr(r), _ptr(p), _ptr(q), _ptr(hd), _ptr(rd), None,
-                                              _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_update')
-
-        def k_scalar(first=0):
-            _lib.check(L.emg3d_dev_pcg_scalar(ncell, K, first, 1e-30, _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()),
-                       'emg3d_dev_pcg_scalar')
-
-        def k_direction(first=0):
-            _lib.check(L.emg3d_dev_pcg_direction(ncell, n, K, first, _ptr(p), _ptr(r), _ptr(hd), _ptr(rd), None, _ptr(table),
-                                                 _stream()), 'emg3d_dev_pcg_direction')
+            rec._regulariser(geo, GN_REG, pcg.p, q, beta=1.0, lam=pcg.lam, pq=pcg.pq, ws=pcg.rws)
 
         def k_hessian():
             nonlocal q
-            q = rec._gradient_block(rec._block_products(dev, 8, block=p, weights=w, reuse=reuse)[1])
+            q = rec._gradient_block(ps.hessian_vec(pcg.p))
+
+        def k_update():
+            pcg.update(0, q)
 
         def start():
-            table.copy_(torch.from_numpy(host))
-            x.zero_()
-            r.copy_(b)
-            k_update(1), k_scalar(1), k_direction(1)
+            pcg.table.copy_(host)
+            pcg.x.zero_()
+            pcg.r.copy_(b)
+            pcg.step(1)
 
         def fused(parts=None):
             """GN_ITERATIONS iterations as gauss_newton_solve runs them; ``parts``: event times per piece are added."""
             start()
             for it in range(1, GN_ITERATIONS + 1):
                 for name, fn in (('hessian pass', k_hessian), ('regulariser', k_reg), ('update', k_update),
-                                 ('scalar step', k_scalar), ('direction', k_direction)):
+                                 ('scalar step', lambda: pcg.scalar(0)), ('direction', lambda: pcg.direction(0))):
                     if parts is None:
                         fn()
                     else:
@@ -668,8 +646,8 @@ def gnsolve_block(rec, say, launches):
                         e.record()
                         parts.setdefault(name, []).append((a, e))
                 if it % GN_CHECK == 0 or it == GN_ITERATIONS:
-                    state = table.cpu().numpy()
-            return x, state[:, 5] / state[:, 1]
+                    state = pcg.table.cpu().numpy()
+            return pcg.x, state[:, 5] / state[:, 1]
 
         tl = torch.from_numpy(lam).to(dev).view(K, 1, 1)
 
@@ -695,36 +673,30 @@ def gnsolve_block(rec, say, launches):
                     rel = (rr / bb).cpu().numpy()
             return xt, rel
 
-        def wall(fn):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn()
-            torch.cuda.synchronize()
-            return 1e3 * (time.perf_counter() - t0) / GN_ITERATIONS, out
         # the kernels alone on a running state (one iteration in, so that p and q hold what an iteration gives them)
         start(), k_hessian(), k_reg()
         elems = K * n * ncell
         shared = (n + 1) * ncell * 8
         for name, fn, nbytes in (('regulariser', k_reg, elems * 24), ('update', k_update, elems * 48 + shared),
-                                 ('direction', k_direction, elems * 24 + shared)):
+                                 ('direction', lambda: pcg.direction(0), elems * 24 + shared)):
             src = torch.empty(nbytes // 16, dtype=torch.float64, device=dev)
             dst = torch.empty_like(src)
-            med, best = timed(fn, launches)
-            cmed, cbest = timed(lambda: dst.copy_(src), launches)
+            med, best, _ = timed(fn, launches)
+            cmed, cbest, _ = timed(lambda: dst.copy_(src), launches)
             say(f"  K = {K}: {name:12s} median {med:7.3f} ms (fastest {best:7.3f}), {nbytes / 1e6:8.1f} MB algorithmic = "
                 f"{nbytes / med / 1e9:5.2f} TB/s; copy that moves the same bytes {cmed:7.3f} ms (fastest {cbest:7.3f}) = "
                 f"{nbytes / cmed / 1e9:5.2f} TB/s; ratio to the copy rate {cmed / med:4.2f}")
             del src, dst
-        med, best = timed(k_scalar, launches)
+        med, best, _ = timed(lambda: pcg.scalar(0), launches)
         say(f"  K = {K}: scalar step  median {med:7.3f} ms (fastest {best:7.3f}), one workgroup")
         # ten iterations, the two routes taking turns
         fused(), composed()                                  # warm-up
         tf, tc = [], []
         for _ in range(GN_ROUNDS):
             t, (xf, relf) = wall(fused)
-            tf.append(t)
+            tf.append(t / GN_ITERATIONS)
             t, (xc, relc) = wall(composed)
-            tc.append(t)
+            tc.append(t / GN_ITERATIONS)
         diff = float((xf - xc).abs().max() / xc.abs().max())
         parts = {}
         fused(parts)
@@ -742,7 +714,7 @@ def gnsolve_block(rec, say, launches):
         torch.cuda.synchronize()
         say(f"  K = {K}: gauss_newton_solve(maxit={GN_ITERATIONS}) with its set-up (hessian_diagonal, diag R, table): "
             f"{1e3 * (time.perf_counter() - t0):.1f} ms, {info['hessian_passes']} passes, states {info['state'].tolist()}")
-        del b, x, r, p, q, reuse
+        del b, q, pcg, ps
 
 
 GN_NORMS = (('weights only', (2.0, 2.0, 2.0, 2.0)), ('norms 1', (1.0, 1.0, 1.0, 1.0)), ('norms general', (0.5, 1.5, 1.2, 0.7)))
@@ -765,17 +737,6 @@ def weighted_block(rec, say, launches):
     wd = torch.from_numpy(rng.uniform(0.2, 5.0, (n, ncell))).to(dev)
     ud = torch.from_numpy(rng.standard_normal((n, ncell))).to(dev)
 
-    def timed(fn, count):
-        ms = []
-        for i in range(count + 2):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i >= 2:
-                ms.append(a.elapsed_time(b))
-        return float(np.median(ms)), float(min(ms))
     hd = rec._hessian_diagonal_block(rec._check_weights(None), dev)[0]
     lam0 = float(hd.mean()) / (GN_REG[1] * float(np.mean(grid.h[0])))
     for K in GN_K:
@@ -792,11 +753,11 @@ def weighted_block(rec, say, launches):
             sparse = any(e != 2.0 for e in norms)
             irls = (wd, norms, ud if sparse else None, GN_EPS if sparse else (0.0, 0.0))
             nbytes = elems * 24 + (2 if sparse else 1) * n * ncell * 8
-            med, best = timed(lambda: rec._regulariser(geo, GN_REG, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws, irls=irls),
-                              launches)
+            med, best, _ = timed(lambda: rec._regulariser(geo, GN_REG, p, q, beta=1.0, lam=dlam, pq=pq, ws=rws, irls=irls),
+                                 launches)
             src = torch.empty(nbytes // 16, dtype=torch.float64, device=dev)
             dst = torch.empty_like(src)
-            cmed, cbest = timed(lambda: dst.copy_(src), launches)
+            cmed, cbest, _ = timed(lambda: dst.copy_(src), launches)
             del src, dst
             say(f"  K = {K}: {name:18s} median {med:7.3f} ms (fastest {best:7.3f}), {nbytes / 1e6:8.1f} MB algorithmic = "
                 f"{nbytes / med / 1e9:5.2f} TB/s; copy that moves the same bytes {cmed:7.3f} ms (fastest {cbest:7.3f}); ratio "
@@ -806,11 +767,7 @@ def weighted_block(rec, say, launches):
                                                            irls_eps=GN_EPS)))
 
         def run(extra, its):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            rec.gauss_newton_solve(b, lam, maxit=its, **kw, **extra)
-            torch.cuda.synchronize()
-            return 1e3 * (time.perf_counter() - t0)
+            return wall(lambda: rec.gauss_newton_solve(b, lam, maxit=its, **kw, **extra))[0]
         for _, extra in routes:
             run(extra, GN_ITERATIONS)                          # warm-up
         per = {name: [] for name, _ in routes}
@@ -834,6 +791,7 @@ def data_preconditioner_block(rec, say, launches):
     of either route as the difference of runs of 2 x and 1 x ``GN_ITERATIONS`` iterations (the set-up drops out), the
     set-up by its steps, and iterations and wall time to ``tol = 1e-3`` at three dampings -- the two routes taking turns."""
     from emg3d_amd import _lib
+    from emg3d_amd._blockpass import _BlockPCG
     from emg3d_amd._device import _ptr, _stream
     L = _lib.lib()
     grid = rec.model.grid
@@ -846,58 +804,24 @@ def data_preconditioner_block(rec, say, launches):
     lam0 = float(hd.sum() / (n * rd.sum()))
     reg = dict(smallness=GN_REG[0], smoothness=GN_REG[1:])
 
-    def timed(fn, count):
-        ms = []
-        for i in range(count + 2):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i >= 2:
-                ms.append(a.elapsed_time(b))
-        return float(np.median(ms)), float(min(ms)), float(max(ms) - min(ms))
-
-    def wall(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return 1e3 * (time.perf_counter() - t0), out
     rng = np.random.default_rng(2)
     for K in GN_K:
         lam = lam0 * 10.0 ** np.linspace(-1, 1, K)
         b = rec.to_device(rng.standard_normal((K, n) + tuple(grid.shape_cells)))
         pre = rec._data_preconditioner_setup(dev, w, rd, None, None)
         M, rank = pre['n_data'], pre['rank']
-        host = np.zeros((K, 8))
-        host[:, 0] = lam
-        host[:, 2], host[:, 3] = 1.0, 2.0
-        pre['table'] = table = torch.from_numpy(host).to(dev)
-        ws_len = L.emg3d_pcg_ws_len(ncell, K)
-        ws = torch.empty(ws_len, dtype=torch.float64, device=dev)
-        pq = torch.ones(K, dtype=torch.float64, device=dev)
-        r, p = b.clone(), b.clone()
-        u, z, g = (torch.zeros_like(b) for _ in range(3))
-        reuse = {}
+        ps = rec._pass(dev, K, 8, w)                       # the pass and the step pieces of gauss_newton_solve
+        pcg = _BlockPCG(ps, lam, b.clone(), 1e-30, None, pre=pre)
+        table, g = pcg.table, torch.zeros_like(b)
+        table[:, 2], table[:, 3] = 1.0, 2.0              # a running state: <r,z> new / old, <p,q>
+        pcg.pq.fill_(1.0)
+        pcg.p.copy_(b)
 
         def k_hessian():
-            rec._gradient_block(rec._block_products(dev, 8, block=p, weights=w, reuse=reuse)[1])
+            rec._gradient_block(ps.hessian_vec(pcg.p))
 
         def k_apply():
-            rec._gradient_block(rec._block_products(dev, 8, block=u, reuse=reuse, apply=pre)[1])
-
-        def k_scale():
-            _lib.check(L.emg3d_dev_pcg_scale(ncell, n, K, 0, _ptr(u), _ptr(r), _ptr(pre['dinv']), 0, _ptr(table), _ptr(pq),
-                                             _stream()), 'emg3d_dev_pcg_scale')
-
-        def k_finish():
-            _lib.check(L.emg3d_dev_pcg_finish(ncell, n, K, 0, _ptr(z), _ptr(u), _ptr(g), _ptr(r), _ptr(pre['dinv']), 0, None,
-                                              _ptr(table), _ptr(pq), _ptr(ws), ws_len, _stream()), 'emg3d_dev_pcg_finish')
-
-        def k_direction():
-            _lib.check(L.emg3d_dev_pcg_direction_z(ncell, n, K, 0, _ptr(p), _ptr(z), _ptr(table), _stream()),
-                       'emg3d_dev_pcg_direction_z')
+            rec._gradient_block(ps.precondition(pcg.u, pre, table))
         d, y = torch.randn((K, M), dtype=torch.float64, device=dev), torch.zeros((K, M), dtype=torch.float64, device=dev)
         fws_len = L.emg3d_data_space_filter_ws_len(rank, K)
         fws = torch.empty(fws_len, dtype=torch.float64, device=dev)
@@ -906,15 +830,16 @@ def data_preconditioner_block(rec, say, launches):
             _lib.check(L.emg3d_dev_data_space_filter(M, rank, K, _ptr(pre['q']), _ptr(pre['eigenvalues']), _ptr(pre['s']),
                                                      _ptr(d), _ptr(y), _ptr(table), _ptr(fws), fws_len, _stream()),
                        'emg3d_dev_data_space_filter')
-        k_scale(), k_hessian(), k_apply()
+        pcg.scale(0), k_hessian(), k_apply()
         for _ in range(2):                                       # the two passes taking turns
             hm, hb, hs = timed(k_hessian, launches)
             am, ab, asp = timed(k_apply, launches)
             say(f"  K = {K}: Hessian pass median {hm:7.3f} ms (fastest {hb:7.3f}, spread {hs:6.3f}); application pass median "
                 f"{am:7.3f} ms (fastest {ab:7.3f}, spread {asp:6.3f}); ratio of the medians {am / hm:4.2f}")
         elems = K * n * ncell
-        for name, fn, nbytes in (('scale', k_scale, elems * 16 + ncell * 8), ('finish', k_finish, elems * 32 + ncell * 8),
-                                 ('direction_z', k_direction, elems * 24)):
+        for name, fn, nbytes in (('scale', lambda: pcg.scale(0), elems * 16 + ncell * 8),
+                                 ('finish', lambda: pcg.finish(0, g), elems * 32 + ncell * 8),
+                                 ('direction_z', lambda: pcg.direction(0), elems * 24)):
             src = torch.empty(nbytes // 16, dtype=torch.float64, device=dev)
             dst = torch.empty_like(src)
             med, best, _ = timed(fn, launches)
@@ -923,7 +848,7 @@ def data_preconditioner_block(rec, say, launches):
                 f"{nbytes / med / 1e9:5.2f} TB/s; copy that moves the same bytes {cmed:7.3f} ms (fastest {cbest:7.3f}); ratio to "
                 f"the copy rate {cmed / med:4.2f}")
             del src, dst
-        p.copy_(b)
+        pcg.p.copy_(b)
         med, best, _ = timed(k_filter, launches)
         src = torch.empty(max(2, M * rank), dtype=torch.float64, device=dev)
         dst = torch.empty_like(src)
@@ -949,7 +874,7 @@ def data_preconditioner_block(rec, say, launches):
             f"{' '.join(f'{t:.3f}' for t in per[True])} ms (mean {np.mean(per[True]):.3f}); data "
             f"{' '.join(f'{t:.3f}' for t in per['data'])} ms (mean {np.mean(per['data']):.3f}); ratio of the means "
             f"{np.mean(per['data']) / np.mean(per[True]):.2f}")
-        del b, r, p, u, z, g, reuse, pre
+        del b, g, pcg, ps, pre
     # what users care about: iterations and wall time to tol 1e-3, one right-hand side, three dampings in one call
     lam = lam0 * np.array(GD_FACTORS)
     b = rec.to_device(rng.standard_normal((1, n) + tuple(grid.shape_cells)))[0]
@@ -1017,10 +942,6 @@ def main():
     def say(line):
         print(line, flush=True)
         lines.append(line)
-
-    def sync():
-        torch.cuda.synchronize()
-        return time.perf_counter()
 
     def hessian_leg(rec):
         head = [lines[0], f"# {wl['label']}; {K} sources x 1 frequency, {len(recs)} receivers; diag Re(J^H J) from the kept "
