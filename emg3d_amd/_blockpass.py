@@ -224,11 +224,13 @@ class _BlockPCG:
     HBM: ``x`` = 0, the residual ``r`` (the right-hand sides as given: updated in place), ``p``, the table of the
     per-column scalars (lambda, <b,b>, <r,z> new / old, <p,q>, <r,r>, iterations, state), the dampings ``lam``, ``pq``,
     the workspaces of the sums (``ws``) and of the regulariser (``rws``). ``diagonals`` = (diag H, diag R) on the device
-    make Jacobi, ``rd_rows`` says that diag R has a row per component (the entry points ``_rd``); ``pre``, the dict of
-    ``_data_preconditioner_setup``, makes the data-space preconditioner with its blocks ``u`` and ``z`` = M r. The three
-    variants are the entry points and argument tails chosen here; everything is queued, nothing is waited for."""
+    make Jacobi, ``rd_rows`` says that diag R has a row per component (the entry points ``_rd``); with ``blocks`` the
+    first of ``diagonals`` holds the packed cell blocks (n (n + 1) / 2, n_cells) instead and makes block-Jacobi (the
+    entry points ``_blk``); ``pre``, the dict of ``_data_preconditioner_setup``, makes the data-space preconditioner with
+    its blocks ``u`` and ``z`` = M r. The four variants are the entry points and argument tails chosen here; everything
+    is queued, nothing is waited for."""
 
-    def __init__(self, ps, lam, r, tol, dmask=None, diagonals=(None, None), rd_rows=False, pre=None):
+    def __init__(self, ps, lam, r, tol, dmask=None, diagonals=(None, None), rd_rows=False, pre=None, blocks=False):
         L, dev = _lib.lib(), ps.dev
         K, n, ncell = r.shape
         self.ps, self.pre, self.tol, self.r, self.shape = ps, pre, float(tol), r, (ncell, n, K)
@@ -244,8 +246,11 @@ class _BlockPCG:
         self.held = diagonals + (dmask,)
         hd, rd, self.mask = (None if t is None else _ptr(t) for t in self.held)
         rd_rows = rd_rows and pre is None
-        sfx = '_rd' if rd_rows else ''
-        diag = (hd, rd) + ((ncell,) if rd_rows else ()) + (self.mask,)
+        if blocks:
+            sfx, diag = '_blk', (hd, ncell, rd, ncell if rd_rows else 0, self.mask)
+        else:
+            sfx = '_rd' if rd_rows else ''
+            diag = (hd, rd) + ((ncell,) if rd_rows else ()) + (self.mask,)
         self.sums = (_ptr(self.table), _ptr(self.pq), _ptr(self.ws), self.ws.numel())
         self._update = ('emg3d_dev_pcg_update' + sfx, diag + self.sums)
         if pre is None:

@@ -13,8 +13,8 @@ LIBDIR = os.path.join(_HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libemg3d_amd.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'emg3d_amd.h')
 SOURCES = [os.path.join(CSRC, f) for f in ('kernels.hip', 'stencil.h', 'launch.h', 'cplx.h', 'receivers.h', 'krylov.h',
-                                            'adjoint.h', 'reciprocal.h', 'hessian.h', 'gram.h', 'block.h',
-                                            'regularise.h', 'precondition.h')] + [HEADER]
+                                            'adjoint.h', 'reciprocal.h', 'hessian.h', 'hessian_blocks.h', 'gram.h',
+                                            'block.h', 'regularise.h', 'pcg_block.h', 'precondition.h')] + [HEADER]
 
 # -ffp-contract: hipcc's own default for HIP, spelled out because csrc/kernels.hip switches contraction off for its
 # line-kernel section and back to THIS mode behind it (`#pragma clang fp contract(fast)`: the pragma can name a mode,
@@ -106,6 +106,11 @@ SIGNATURES = {
     'emg3d_dev_edges_to_cells': (_ci, [_ci] * 4 + [_vp] * 3 + [ctypes.c_double] * 2 + [_vp] * 4 + [_vp]),
     'emg3d_dev_hessian_diagonal': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci, _vp] + [_ci] * 3 + [ctypes.c_double] +
                                    [_vp, _vp, _sz, _vp]),
+    # the cell blocks of the Hessian: the arguments of emg3d_dev_hessian_diagonal
+    'emg3d_dev_hessian_cell_blocks': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci, _vp] + [_ci] * 3 + [ctypes.c_double] +
+                                      [_vp, _vp, _sz, _vp]),
+    'emg3d_dev_hessian_cell_blocks_sp': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci, _vp] + [_ci] * 3 +
+                                         [ctypes.c_double] + [_vp, _vp, _sz, _vp]),
     'emg3d_data_gram_ws_len': (_sz, [_ci] * 6),
     'emg3d_dev_data_gram': (_ci, [_ci] * 4 + [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 +
                             [_vp, _sz, _ci, _vp, _sz, _ci] + [ctypes.c_double] * 2 + [_ci] * 3 +
@@ -140,6 +145,9 @@ SIGNATURES = {
                                                       [_vp, _vp, _sz, _vp, _sz] + [ctypes.c_double] * 6 + [_ci, _vp, _vp]),
     'emg3d_dev_pcg_update_rd': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 6 + [_sz] + [_vp] * 4 + [_sz, _vp]),
     'emg3d_dev_pcg_direction_rd': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 4 + [_sz] + [_vp] * 3),
+    # block-Jacobi from the cell blocks of the Hessian
+    'emg3d_dev_pcg_update_blk': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 5 + [_sz, _vp, _sz] + [_vp] * 4 + [_sz, _vp]),
+    'emg3d_dev_pcg_direction_blk': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 3 + [_sz, _vp, _sz] + [_vp] * 3),
     'emg3d_pcg_table_len': (_sz, [_ci]),
     'emg3d_pcg_ws_len': (_sz, [_sz, _ci]),
     'emg3d_dev_pcg_update': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 10 + [_sz, _vp]),

@@ -2834,7 +2834,9 @@ int emg3d_core_solve(void *amat, void *bvec, int n, int is_complex)
 #include "adjoint.h"
 #include "reciprocal.h"
 #include "hessian.h"
+#include "hessian_blocks.h"
 #include "gram.h"
 #include "block.h"
 #include "regularise.h"
+#include "pcg_block.h"
 #include "precondition.h"

@@ -623,6 +623,10 @@ class ReciprocalSensitivity(Sensitivity):
     ``regulariser_vec_block`` applies the smallness-plus-roughness operator ``R`` on its own. Beside Jacobi it has a
     data-space preconditioner, ``precondition='data'``: the Woodbury inverse of ``lambda_k diag R + J^T W J`` from one
     ``data_gram`` and one eigen-decomposition per call, applied by one more pass over the kept fields.
+    For models with several properties per cell (VTI, HTI, tri-axial) ``hessian_cell_blocks`` gives the n x n blocks of
+    ``Re(J^H W J)`` that couple the properties of one cell, in the one pass of ``hessian_diagonal``
+    (``emg3d_dev_hessian_cell_blocks``), and ``precondition='block'`` inverts them per cell inside the PCG kernels
+    (block-Jacobi, ``emg3d_dev_pcg_update_blk`` / ``_direction_blk``).
     The outer inversion loop (line search, observed data, choice of the damping) is the user's.
 
     field_dtype: ``'double'`` (default) keeps the fields as they are solved, ``n_edges x 16 B`` each. ``'single'``
@@ -894,13 +898,15 @@ class ReciprocalSensitivity(Sensitivity):
         self.forward()
         return self.from_device(self._hessian_diagonal_block(w, dev))[0]
 
-    def _hessian_diagonal_block(self, w, dev):
-        """``hessian_diagonal`` for the checked weights ``w`` as a device block of one column, (1, n, n_cells)."""
+    def _hessian_rows(self, entry, nrows, w, dev):
+        """The frequency loop of ``hessian_diagonal`` and ``hessian_cell_blocks``: ``nrows`` rows of n_cells zeros in HBM
+        into which one call of the C entry point ``entry`` (or its ``_sp`` sibling) per frequency accumulates, for the
+        checked weights ``w``; a frequency whose weights are all zero is skipped. Without the chain factors."""
         import torch
         from emg3d_amd import _lib
         from emg3d_amd._device import _ptr, _stream
         rx, ry, rz = _EXPAND[self.model.case]
-        nrows, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
+        ncell = self.model.grid.n_cells
         nx, ny, nz = self.model.grid.shape_cells
         h = torch.zeros(nrows * ncell, dtype=torch.float64, device=dev)
         for fname, mine, gkey, grid, vol, plan, smu0 in self._per_frequency():
@@ -909,13 +915,58 @@ class ReciprocalSensitivity(Sensitivity):
                 continue
             estack, xstack = self._fields_of(fname)
             wdev = torch.from_numpy(np.ascontiguousarray(wf)).to(dev)
-            kernel, name = self._entry('emg3d_dev_hessian_diagonal', estack)
+            kernel, name = self._entry(entry, estack)
             _lib.check(kernel(
                 nx, ny, nz, int(estack.is_complex()), _ptr(estack), estack.stride(0), len(estack),
                 _ptr(xstack), xstack.stride(0), len(xstack), _ptr(wdev), rx, ry, rz, abs(smu0) ** 2, _ptr(vol), _ptr(h),
                 ncell, _stream()), name)
+        return h.view(nrows, ncell)
+
+    def _hessian_diagonal_block(self, w, dev):
+        """``hessian_diagonal`` for the checked weights ``w`` as a device block of one column, (1, n, n_cells)."""
+        nrows = _NCOMP[self.model.case]
         d = self._chain_factors(dev)
-        return h.view(1, nrows, ncell) * (d * d)
+        return self._hessian_rows('emg3d_dev_hessian_diagonal', nrows, w, dev)[None] * (d * d)
+
+    @staticmethod
+    def _packed_rows(n):
+        """(p, q) of the packed rows of the cell blocks: the diagonal first, then (0,1), (0,2), (1,2)."""
+        return [(p, p) for p in range(n)] + [(p, q) for q in range(1, n) for p in range(q)]
+
+    def hessian_cell_blocks(self, weights=None, on_device=False):
+        """The blocks of the Gauss-Newton Hessian ``Re(J^H W J)`` that couple the ``n`` properties of ONE cell:
+        ``B[p, q, c] = sum_i w_i Re(conj(J_i[p, c]) J_i[q, c])``, shape ``(n, n) + shape_cells`` (cells ordered as
+        ``jtvec`` orders them), symmetric bit for bit; its diagonal ``B[p, p]`` is ``hessian_diagonal``. It is the
+        block-Jacobi preconditioner of a multi-parameter Gauss-Newton iteration (``gauss_newton_solve(precondition=
+        'block')``) and a diagnostic: where ``B[p, q] / sqrt(B[p, p] B[q, q])`` is close to +-1 the data cannot
+        separate the two properties. ``weights`` as for ``hessian_diagonal``. ``on_device=True``: the packed device
+        tensor ``(n (n + 1) / 2, n_cells)`` instead, float64, rows (0,0) .. (n-1,n-1), then (0,1), (0,2), (1,2), cells
+        x fastest. Without a solve: per frequency one ``emg3d_dev_hessian_cell_blocks`` over the kept fields, the same
+        bytes as ``hessian_diagonal`` reads (a frequency whose weights are all zero is skipped). Every
+        computational grid must be the model grid."""
+        w = self._check_weights(weights)                        # raises before any GPU work
+        self._require_model_grid('hessian_cell_blocks', 'before the product is taken')
+        dev = self._device()
+        self.forward()
+        packed = self._hessian_cell_blocks_packed(w, dev)
+        if on_device:
+            return packed
+        n, shape = _NCOMP[self.model.case], tuple(self.model.grid.shape_cells)
+        rows = packed.cpu().numpy()
+        out = np.empty((n, n) + shape, order='F')
+        for m, (p, q) in enumerate(self._packed_rows(n)):
+            out[p, q] = out[q, p] = rows[m].reshape(shape, order='F')
+        return out
+
+    def _hessian_cell_blocks_packed(self, w, dev):
+        """``hessian_cell_blocks`` for the checked weights ``w``: the packed device tensor, row (p, q) times the chain
+        factors ``d_p d_q``."""
+        import torch
+        n = _NCOMP[self.model.case]
+        rows = self._packed_rows(n)
+        d = self._chain_factors(dev)
+        h = self._hessian_rows('emg3d_dev_hessian_cell_blocks', len(rows), w, dev)
+        return h * torch.stack([d[p] * d[q] for p, q in rows])
 
     def hessian_vec(self, vector, weights=None):
         """Gauss-Newton Hessian times a model-shaped real ``vector``: ``jtvec({pair: weights[pair] * jvec(vector)[pair]})``,
@@ -1442,17 +1493,22 @@ class ReciprocalSensitivity(Sensitivity):
 
     def _pcg(self, dev, r, lam, kc, w, geo, alphas, irls, precondition, data_rank=None, tol=0.0):
         """The ``_BlockPCG`` of ``gauss_newton_solve`` for the device residual block ``r`` (K, n, n_cells) after the
-        set-up of its preconditioner -- ``precondition``: ``'data'``, True (Jacobi: the two diagonals) or False --, on a
-        new ``_BlockPass``: every buffer of the iteration is allocated here, behind the temporaries of the set-up.
-        (``tol`` is read by the scalar step alone.)"""
+        set-up of its preconditioner -- ``precondition``: ``'data'``, ``'block'`` (block-Jacobi: the packed cell blocks
+        and diag R; one component per cell: Jacobi), True (Jacobi: the two diagonals) or False --, on a new
+        ``_BlockPass``: every buffer of the iteration is allocated here, behind the temporaries of the set-up. (``tol``
+        is read by the scalar step alone.)"""
         from emg3d_amd._blockpass import _BlockPCG
         hd = rd = pre = None
+        blocks = precondition == 'block' and r.shape[1] > 1
         if precondition == 'data':
             pre = self._data_preconditioner_setup(dev, w, self._regulariser_diagonal(geo, alphas, irls, dev), geo[6], data_rank)
+        elif blocks:
+            hd = self._hessian_cell_blocks_packed(w, dev).contiguous()
+            rd = self._regulariser_diagonal(geo, alphas, irls, dev)
         elif precondition:
             hd = self._hessian_diagonal_block(w, dev)[0].contiguous()
             rd = self._regulariser_diagonal(geo, alphas, irls, dev)
-        return _BlockPCG(self._pass(dev, len(lam), kc, w), lam, r, tol, geo[6], (hd, rd), irls is not None, pre)
+        return _BlockPCG(self._pass(dev, len(lam), kc, w), lam, r, tol, geo[6], (hd, rd), irls is not None, pre, blocks)
 
     def gauss_newton_solve(self, rhs, dampings, weights=None, smallness=0.0, smoothness=(1.0, 1.0, 1.0), active=None,
                            tol=1e-3, maxit=50, precondition=True, check_every=4, on_device=None, columns_per_pass=8, *,
@@ -1482,7 +1538,13 @@ class ReciprocalSensitivity(Sensitivity):
             the inversion.
         precondition: Jacobi, ``1 / (hessian_diagonal(weights) + dampings[k] diag R)``, formed inside the kernels from
             the two diagonals, which all columns share (where that sum is not positive: 1). Needs every computational
-            grid to be the model grid, as ``hessian_diagonal`` does. False: no preconditioner. ``'data'``: the data-space
+            grid to be the model grid, as ``hessian_diagonal`` does. False: no preconditioner. ``'block'``: block-Jacobi
+            (DESIGN.md 4.20): per cell the inverse of the ``n x n`` block ``hessian_cell_blocks(weights)[:, :, c] +
+            dampings[k] diag R``, by a Cholesky factorisation in registers inside the kernels
+            (``emg3d_dev_pcg_update_blk`` / ``_direction_blk``); a cell whose block is not positive definite in floating
+            point takes the Jacobi rule. It removes the cross-talk of the properties of one cell (sigma_h and sigma_v of
+            VTI), which Jacobi ignores; the set-up is one pass over the kept fields, as for Jacobi, and the limits are
+            Jacobi's. A model with one property per cell (``n = 1``) takes the Jacobi route itself. ``'data'``: the data-space
             (Woodbury) preconditioner. ``H = J^T W J`` has rank at most M, the number of real data, so
             ``(lambda_k diag R + H)^-1`` is ``diag R^-1 / lambda_k`` minus a correction through an M x M matrix: once
             per call ``data_gram(1 / diag R)`` is formed, scaled by the square roots of the weights and decomposed on the
@@ -1525,9 +1587,12 @@ class ReciprocalSensitivity(Sensitivity):
         K = len(lam)
         on_dev, single, b = self._check_rhs(rhs, K)
         by_data = isinstance(precondition, str) and precondition == 'data'
+        by_block = isinstance(precondition, str) and precondition == 'block'
         if by_data:
             data_rank = self._check_data_rank(data_rank)
             self._require_data_preconditioner()
+        elif by_block:
+            self._require_model_grid("gauss_newton_solve(precondition='block')", 'before the product is taken')
         elif precondition:
             self._require_model_grid('gauss_newton_solve(precondition=True)', 'before the modulus is taken')
         dev = self._device()
@@ -1537,7 +1602,7 @@ class ReciprocalSensitivity(Sensitivity):
         irls = self._upload_irls(irls, dev)
         geo = self._regulariser_geometry(mask, dev)
         pcg = self._pcg(dev, (b.expand(K, n, ncell) if single else b).clone(), lam, kc, w, geo, alphas, irls,
-                        'data' if by_data else bool(precondition), data_rank, tol)
+                        'data' if by_data else 'block' if by_block else bool(precondition), data_rank, tol)
 
         def look():
             t = pcg.table.cpu().numpy()

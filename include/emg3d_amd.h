@@ -474,6 +474,20 @@ int emg3d_dev_hessian_diagonal(int nx, int ny, int nz, int is_complex, const voi
                                int ns, const void *x, size_t x_stride, int nr, const double *weights,
                                int row_x, int row_y, int row_z, double scale, const double *volumes,
                                double *h, size_t h_stride, void *stream);
+/* The n x n blocks of the Gauss-Newton Hessian that couple the components of ONE cell,
+ * n = max(row) + 1: with Z_p = sum_{d: row_d = p} Z_{s,r,d}(c) of emg3d_dev_hessian_diagonal,
+ *     h[m * h_stride + c] += scale (V_c / 4)^2 sum_{s,r} weights[s * nr + r] Re( conj(Z_p) Z_q )
+ * (real fields: Z_p Z_q) for the n (n + 1) / 2 packed rows m = (p, q), p <= q: the diagonal (0,0) ..
+ * (n-1,n-1) first -- what emg3d_dev_hessian_diagonal adds --, then (0,1) and, for n = 3, (0,2), (1,2).
+ * Arguments and checks as there; in addition every row below n must have a direction: a row map such
+ * as (0, 2, 2) is EMG3D_ERR_BADARG. n = 1: one row, the diagonal. One pass over the stacks, the same
+ * bytes as the diagonal: every direction is staged once per tile of sources and receivers and the pair
+ * sums of all rows stay in registers (csrc/hessian_blocks.h; n = 3 works on tiles of 4 x 2). Plain
+ * fp64, no atomics, sums in an order fixed by the sizes. */
+int emg3d_dev_hessian_cell_blocks(int nx, int ny, int nz, int is_complex, const void *e, size_t e_stride,
+                                  int ns, const void *x, size_t x_stride, int nr, const double *weights,
+                                  int row_x, int row_y, int row_z, double scale, const double *volumes,
+                                  double *h, size_t h_stride, void *stream);
 /* One block of the data-space Gauss-Newton matrix G^ = J^ diag(m) J^T between the data
  * of a side A and a side B -- two frequencies, or one and the same --, from the kept stacks of either
  * side (conventions as above). J^ has the rows Re J_i, i = s * nr + r, and, for complex fields (c = 2;
@@ -528,6 +542,11 @@ int emg3d_dev_hessian_diagonal_sp(int nx, int ny, int nz, int is_complex, const 
                                   int ns, const void *x, size_t x_stride, int nr, const double *weights,
                                   int row_x, int row_y, int row_z, double scale, const double *volumes,
                                   double *h, size_t h_stride, void *stream);
+/* emg3d_dev_hessian_cell_blocks_sp: NARROW e, x; everything else as for emg3d_dev_hessian_diagonal_sp. */
+int emg3d_dev_hessian_cell_blocks_sp(int nx, int ny, int nz, int is_complex, const void *e, size_t e_stride,
+                                     int ns, const void *x, size_t x_stride, int nr, const double *weights,
+                                     int row_x, int row_y, int row_z, double scale, const double *volumes,
+                                     double *h, size_t h_stride, void *stream);
 /* emg3d_dev_data_gram_sp: NARROW e_a, x_a, e_b, x_b (both sides). fp64: the scales, model_weights,
  * volumes, out, ws. Staging as in emg3d_dev_hessian_diagonal_sp; the panels are fp64. */
 int emg3d_dev_data_gram_sp(int nx, int ny, int nz, int is_complex, const void *e_a, size_t e_a_stride,
@@ -680,6 +699,21 @@ int emg3d_dev_pcg_update_rd(size_t n_cells, int vec_per_col, int ncol, int first
 int emg3d_dev_pcg_direction_rd(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *r,
                                const double *hdiag, const double *rdiag, size_t rdiag_stride,
                                const unsigned char *mask, const double *table, void *stream);
+/* emg3d_dev_pcg_update / emg3d_dev_pcg_direction with the block-Jacobi preconditioner: per cell c
+ * z_c = (B_c + lambda diag(rd_c))^-1 r_c, B_c the symmetric vec_per_col x vec_per_col block of the packed rows of
+ * emg3d_dev_hessian_cell_blocks (hblocks, rows hblocks_stride >= n_cells apart, already times the chain factors), rd
+ * as for the _rd entries. vec_per_col in {2, 3}: 1 is refused, the entries above serve it. A thread takes a cell and
+ * all its components, factorises by Cholesky in registers and solves; where a pivot is not finite and > 0 the cell
+ * falls back to the Jacobi rule of the entries above on the diagonal rows, component by component. Everything else
+ * -- alpha, beta, frozen columns, masks, the layout of ws -- as there; emg3d_dev_pcg_scalar follows unchanged.
+ * EMG3D_ERR_BADARG, nothing launched: hblocks or rdiag NULL, a stride below n_cells (rdiag_stride may be 0). */
+int emg3d_dev_pcg_update_blk(size_t n_cells, int vec_per_col, int ncol, int first, double *x, double *r, const double *p,
+                             const double *q, const double *hblocks, size_t hblocks_stride, const double *rdiag,
+                             size_t rdiag_stride, const unsigned char *mask, const double *table, const double *pq,
+                             double *ws, size_t ws_len, void *stream);
+int emg3d_dev_pcg_direction_blk(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *r,
+                                const double *hblocks, size_t hblocks_stride, const double *rdiag, size_t rdiag_stride,
+                                const unsigned char *mask, const double *table, void *stream);
 /* The data-space (Woodbury) preconditioner of the block PCG above: with dinv = 1 / diag R (1 where
  * that is not positive, 0 on inactive cells; vec_per_col rows dinv_stride doubles apart, stride 0: one row for all
  * components), s = sqrt(data weights) and the eigenpairs (Q, L) of diag(s) J^ diag(dinv) J^T diag(s), per running column

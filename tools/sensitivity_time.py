@@ -34,9 +34,13 @@ Leg ``gndata``: the data-space (Woodbury) preconditioner of ``gauss_newton_solve
 8: the application pass beside the Hessian pass, its vector kernels and the filter beside a copy of their bytes, an
 iteration of either route, the set-up by its steps, and iterations and wall time to ``tol = 1e-3`` at three dampings, the
 two routes taking turns for five rounds. Writes profiles/data_preconditioner_times.txt.
+Leg ``blocks``: the cell blocks of the Hessian and block-Jacobi on the workload's VTI model: the kernel
+``emg3d_dev_hessian_cell_blocks`` beside ``emg3d_dev_hessian_diagonal`` on the same inputs, taking turns (HIP events), an
+iteration of ``gauss_newton_solve`` with ``'block'`` beside ``True``, and iterations and wall time to ``tol = 1e-3`` of
+``True``, ``'block'`` and ``'data'`` at the three dampings of the ``gndata`` leg. Writes profiles/hessian_blocks_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
-                                     [--leg all|products|hessian|gram|single|block|gnsolve|gndata]
+                                     [--leg all|products|hessian|gram|single|block|gnsolve|gndata|blocks]
                                      [--field-dtype double|single]
                                      [--out profiles/sensitivity_times.txt]
                                      [--hessian-out profiles/hessian_diagonal_times.txt]
@@ -46,6 +50,7 @@ two routes taking turns for five rounds. Writes profiles/data_preconditioner_tim
                                      [--gnsolve-out profiles/gauss_newton_solve_times.txt]
                                      [--weighted-out profiles/weighted_regulariser_times.txt]
                                      [--gndata-out profiles/data_preconditioner_times.txt]
+                                     [--blocks-out profiles/hessian_blocks_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -892,13 +897,115 @@ def data_preconditioner_block(rec, say, launches):
                 f"{info['hessian_passes']} + {info['preconditioner_passes']} passes, {t:.1f} ms with the set-up")
 
 
+def cell_blocks_block(rec, say, launches):
+    """The cell blocks of the Hessian and block-Jacobi on the kept fields of ``rec``: the two kernels on
+    the same inputs taking turns, an iteration of ``gauss_newton_solve`` with ``'block'`` beside ``True`` as the
+    difference of runs of 2 x and 1 x ``GN_ITERATIONS`` iterations, and iterations and wall time to ``tol = 1e-3`` of the
+    three preconditioners at the dampings of ``data_preconditioner_block``."""
+    from emg3d_amd import _lib
+    from emg3d_amd._device import _ptr, _stream
+    L = _lib.lib()
+    (E, X), = rec._stacks.values()
+    ns, nr, nedges = len(E), len(X), E.shape[1]
+    grid = rec.model.grid
+    nx, ny, nz = grid.shape_cells
+    n, ncell = gradient._NCOMP[rec.model.case], grid.n_cells
+    rows3 = gradient._EXPAND[rec.model.case]
+    npack = n * (n + 1) // 2
+    dev = E.device
+    vol = rec._computational(rec.pairs[0])[3]
+    wd = torch.ones(ns * nr, dtype=torch.float64, device=dev)
+    h = torch.zeros(npack * ncell, dtype=torch.float64, device=dev)
+    sp, el = gradient.ReciprocalSensitivity._sp(E), E.element_size()
+
+    def kernel(name):
+        name += sp
+        fn = getattr(L, name)
+        return lambda: _lib.check(fn(nx, ny, nz, 1, _ptr(E), E.stride(0), ns, _ptr(X), X.stride(0), nr, _ptr(wd), *rows3, 1.0,
+                                     _ptr(vol), _ptr(h), ncell, _stream()), name)
+    what = [('hessian_diagonal', kernel('emg3d_dev_hessian_diagonal'), n),
+            ('hessian_cell_blocks', kernel('emg3d_dev_hessian_cell_blocks'), npack)]
+    ms = {name: [] for name, _, _ in what}
+    for r in range(launches + 3):                    # three warm-up rounds; the two take turns
+        for name, fn, _ in what:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if r >= 3:
+                ms[name].append(a.elapsed_time(b))
+    say(f"kernels alone: {nx} x {ny} x {nz} cells, {nedges:,} edges, ns {ns}, nr {nr}, {E.dtype}, rows {rows3}: both read "
+        f"(ns + nr) {el} n = {(ns + nr) * el * nedges:,} B of fields; the diagonal stages every direction once per row and "
+        f"tile, the blocks once per tile, and form {npack} products per pair instead of {n}")
+    med = {}
+    for name, _, nrows in what:
+        q = np.percentile(ms[name], [50, 25, 75, 0, 100])
+        med[name] = q[0]
+        nbytes = (ns + nr) * el * nedges + 8 * ncell + 16 * nrows * ncell
+        say(f"  {name:20s} median {q[0]:8.4f} ms (quartiles {q[1]:.4f} .. {q[2]:.4f}, range {q[3]:.4f} .. {q[4]:.4f}; "
+            f"{len(ms[name])} launches, HIP events) = {nbytes / q[0] / 1e9:7.3f} TB/s on algorithmic bytes ({nrows} rows of h)")
+    say(f"  ratio of the medians, cell blocks / diagonal: {med['hessian_cell_blocks'] / med['hessian_diagonal']:.2f}")
+    t, B = wall(lambda: rec.hessian_cell_blocks(on_device=True))
+    t, B = wall(lambda: rec.hessian_cell_blocks(on_device=True))
+    corr = (B[n] / torch.sqrt(B[0] * B[1])).abs()
+    corr = corr[torch.isfinite(corr)]
+    say(f"method hessian_cell_blocks(on_device=True): {t:.3f} ms; |B_01| / sqrt(B_00 B_11): median "
+        f"{float(corr.median()):.3f}, 90 % {float(torch.quantile(corr[::8], 0.9)):.3f}, max {float(corr.max()):.3f}")
+    del B, corr
+
+    w = rec._check_weights(None)
+    geo = rec._regulariser_geometry(None, dev)
+    hd = rec._hessian_diagonal_block(w, dev)[0]
+    rd = rec._regulariser_diagonal(geo, GN_REG, None, dev)
+    lam0 = float(hd.sum() / (n * rd.sum()))
+    del hd, rd
+    reg = dict(smallness=GN_REG[0], smoothness=GN_REG[1:])
+    rng = np.random.default_rng(2)
+    routes = ((True, 'Jacobi'), ('block', 'block '))
+    for K in GN_K:
+        lam = lam0 * 10.0 ** np.linspace(-1, 1, K)
+        b = rec.to_device(rng.standard_normal((K, n) + tuple(grid.shape_cells)))
+
+        def run(route, its):
+            return rec.gauss_newton_solve(b, lam, tol=1e-30, maxit=its, check_every=GN_CHECK, precondition=route, **reg)
+        for route, _ in routes:
+            run(route, 2)                                        # warm-up
+        per = {route: [] for route, _ in routes}
+        for _ in range(GN_ROUNDS):
+            for route, _ in routes:
+                t1, _ = wall(lambda: run(route, GN_ITERATIONS))
+                t2, _ = wall(lambda: run(route, 2 * GN_ITERATIONS))
+                per[route].append((t2 - t1) / GN_ITERATIONS)
+        say(f"  K = {K}: per iteration (wall, (2 x {GN_ITERATIONS} - {GN_ITERATIONS}) iterations / {GN_ITERATIONS}), rounds: Jacobi "
+            f"{' '.join(f'{t:.3f}' for t in per[True])} ms (mean {np.mean(per[True]):.3f}); block "
+            f"{' '.join(f'{t:.3f}' for t in per['block'])} ms (mean {np.mean(per['block']):.3f}); ratio of the means "
+            f"{np.mean(per['block']) / np.mean(per[True]):.2f}")
+        del b
+    lam = lam0 * np.array(GD_FACTORS)
+    b = rec.to_device(rng.standard_normal((1, n) + tuple(grid.shape_cells)))[0]
+    routes += (('data', 'data  '),)
+
+    def solve(route):
+        return rec.gauss_newton_solve(b, lam, tol=1e-3, maxit=GD_MAXIT, check_every=GN_CHECK, precondition=route, **reg)
+    for route, _ in routes:
+        rec.gauss_newton_solve(b, lam, tol=1e-3, maxit=2, precondition=route, **reg)
+    for _ in range(3):
+        for route, label in routes:
+            t, (_, info) = wall(lambda: solve(route))
+            say(f"  to tol 1e-3, dampings {GD_FACTORS} x tr H / tr R ({lam0:.3e}), maxit {GD_MAXIT}: {label} iterations "
+                f"{info['iterations'].tolist()}, states {info['state'].tolist()}, relative residuals "
+                f"{[f'{v:.1e}' for v in info['relative_residual']]}, {info['hessian_passes']} + "
+                f"{info['preconditioner_passes']} passes, {t:.1f} ms with the set-up")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
-    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block', 'gnsolve', 'gndata'),
+    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block', 'gnsolve', 'gndata', 'blocks'),
                     default='all',
                     help="products: the inner iteration four ways and its two reductions; hessian: hessian_diagonal against "
                          "the row-by-row route (needs only the set-up of ReciprocalSensitivity); gram: data_gram against the "
@@ -907,7 +1014,8 @@ def main():
                          "block kernels and hessian_vec_block against K single calls (not part of 'all'); gnsolve: an "
                          "iteration of gauss_newton_solve, its kernels and the same iteration from torch operations (not "
                          "part of 'all'); gndata: the data-space preconditioner of gauss_newton_solve beside Jacobi (not part "
-                         "of 'all')")
+                         "of 'all'); blocks: the cell blocks of the Hessian beside its diagonal and block-Jacobi beside Jacobi "
+                         "and the data-space preconditioner (not part of 'all')")
     ap.add_argument('--field-dtype', choices=('double', 'single'), default='double',
                     help="how ReciprocalSensitivity keeps its fields in the reciprocal, hessian and gram legs")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
@@ -918,6 +1026,7 @@ def main():
     ap.add_argument('--gnsolve-out', default=os.path.join(ROOT, 'profiles', 'gauss_newton_solve_times.txt'))
     ap.add_argument('--weighted-out', default=os.path.join(ROOT, 'profiles', 'weighted_regulariser_times.txt'))
     ap.add_argument('--gndata-out', default=os.path.join(ROOT, 'profiles', 'data_preconditioner_times.txt'))
+    ap.add_argument('--blocks-out', default=os.path.join(ROOT, 'profiles', 'hessian_blocks_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -1046,6 +1155,22 @@ def main():
         rec.release()
         os.makedirs(os.path.dirname(os.path.abspath(args.gndata_out)), exist_ok=True)
         with open(args.gndata_out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
+    if args.leg == 'blocks':
+        lines[1] = (f"# {wl['label']}; {K} sources x 1 frequency, {len(recs)} receivers; the cell blocks of Re(J^H J) beside its "
+                    f"diagonal, and (H + lambda_k R) x_k = b_k with block-Jacobi beside Jacobi and the data-space preconditioner, "
+                    f"smallness {GN_REG[0]}, smoothness {GN_REG[1:]}, all weights one, field_dtype 'double'; times in ms")
+        if ncomp < 2:
+            raise SystemExit("--leg blocks needs a model with more than one property per cell (VTI, HTI, triaxial)")
+        rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
+                                             batch=K)
+        rec.forward()
+        say(f"{rec!r}")
+        cell_blocks_block(rec, say, args.launches)
+        rec.release()
+        os.makedirs(os.path.dirname(os.path.abspath(args.blocks_out)), exist_ok=True)
+        with open(args.blocks_out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
         return
     if args.leg in ('hessian', 'gram'):
