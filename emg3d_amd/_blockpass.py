@@ -1,7 +1,7 @@
-"""Passes over the kept fields of ``gradient.ReciprocalSensitivity`` for a block of K columns, and
-the block PCG of ``gauss_newton_solve`` on top of them. Host code: every kernel is an entry
-point of the library; between the kernels of a pass the host queues torch operations on (K, ns, nr) and waits for
-nothing."""
+"""Passes over the kept fields of ``gradient.ReciprocalSensitivity`` for a block of K columns, the
+block PCG of ``gauss_newton_solve`` on top of them and the orthonormalisation of a device block
+(DESIGN.md 4.21). Host code: every kernel is an entry point of the library; between the kernels of a pass the host
+queues torch operations on (K, ns, nr) and waits for nothing."""
 import types
 
 import numpy as np
@@ -134,6 +134,16 @@ class _BlockPass:
         self.grad = torch.zeros((self.K, 3, self.rec.model.grid.n_cells), dtype=torch.float64, device=self.dev)
         return self.grad
 
+    def shrink(self, K):
+        """Fewer columns from now on (the block of a subspace method has lost rank), for ``jvec``, ``jtvec`` and
+        ``hessian_vec``: the first K rows of ``grad`` and of the results of ``dots``; the scratch of a group stays as it
+        is. The buffers of ``precondition`` (``d``, ``y``, ``fws``) are sized by the K of their first use and are not
+        covered: a pass that has applied the preconditioner is not shrunk."""
+        assert self.d is None and K <= self.K
+        self.K = K
+        self.grad = None if self.grad is None else self.grad[:K]
+        self.res = {fname: res[:K] for fname, res in self.res.items()}
+
     # --------------------------------------------------------------------------- products ---
     def jvec(self, block):
         """J v for the K columns of the device block: dict frequency name -> device tensor (K, ns, nr)."""
@@ -217,6 +227,66 @@ class _BlockPass:
             coef = torch.complex(y[:, re], -y[:, im]).reshape(jv[f.fname].shape)       # conj, as for ``jtvec``
             self.combine(f, coef, list(range(K)))
         return grad
+
+
+def _svqb_rotation(G):
+    """The matrix T (K, r) of one SVQB step (Stathopoulos and Wu) from the Gram matrix ``G = Y^T Y`` (K, K) of a block:
+    with ``D = diag G``, ``D^-1/2 G D^-1/2 = Z L Z^T`` (``eigh``, fp64) and the r eigenvalues above ``K eps max L``,
+    largest first, ``T = D^-1/2 Z L^-1/2`` -- the columns of ``Y T`` are orthonormal. The scaling takes the norms of the
+    columns out of the spectrum, the threshold reveals the rank: r < K for a block of dependent columns, 0 for a block
+    of zeros. A column whose norm is 0 (or not finite) gets a row of zeros."""
+    K = len(G)
+    d = np.diag(G)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        scale = np.where((d > 0) & np.isfinite(d), 1.0 / np.sqrt(d), 0.0)
+    lam, Z = np.linalg.eigh(G * scale[:, None] * scale[None, :])
+    lam, Z = lam[::-1], Z[:, ::-1]
+    r = int(np.sum(lam > K * np.finfo(float).eps * max(lam[0], 0.0))) if lam[0] > 0 else 0
+    return np.ascontiguousarray(scale[:, None] * Z[:, :r] / np.sqrt(lam[:r])[None, :])
+
+
+class _BlockOrth:
+    """Makes the columns of a device block orthonormal in place: SVQB on the Gram matrix, applied twice.
+    Per application one ``emg3d_dev_block_gram``, the download of (K, K), ``_svqb_rotation`` on the host, the upload of
+    T and one ``emg3d_dev_block_rotate`` -- the first from the block into the scratch, the second back. The object owns
+    the scratch, one second block of ``kmax`` columns, the workspace of the sums and the two small matrices; every call
+    uses them again. ``rotate`` serves other products ``Y T`` of the caller (into the scratch)."""
+
+    def __init__(self, dev, kmax, n):
+        need, free = kmax * n * 8, free_hbm(dev)
+        if need > free:
+            raise MemoryError(f"ReciprocalSensitivity: the second block of {kmax} columns that the orthonormalisation "
+                              f"needs takes {need:,} B of HBM, {free:,} B are free.")
+        self.n, self.kmax = n, kmax
+        self.other = torch.empty((kmax, n), dtype=torch.float64, device=dev)
+        self.g, self.t = (torch.empty(kmax * kmax, dtype=torch.float64, device=dev) for _ in range(2))
+        self.ws = torch.empty(_lib.lib().emg3d_block_gram_ws_len(n, kmax), dtype=torch.float64, device=dev)
+
+    def gram(self, block):
+        """``block`` (K, n) -> its Gram matrix (K, K) on the host."""
+        K = len(block)
+        _call('emg3d_dev_block_gram', self.n, K, _ptr(block), block.stride(0), _ptr(self.g), _ptr(self.ws))
+        return self.g[:K * K].cpu().numpy().reshape(K, K)
+
+    def rotate(self, block, T, out=None):
+        """``out`` (default: the scratch) = ``block`` (K, n) times the host matrix T (K, r): (r, n)."""
+        K, r = T.shape
+        out = self.other[:r] if out is None else out
+        self.t[:K * r].copy_(torch.from_numpy(np.ascontiguousarray(T, dtype=np.float64)).view(-1))
+        _call('emg3d_dev_block_rotate', self.n, K, r, _ptr(block), block.stride(0), _ptr(self.t), _ptr(out), out.stride(0))
+        return out
+
+    def __call__(self, block):
+        """``block`` (K, n), K <= kmax, contiguous: (its first ``rank`` rows, now orthonormal and spanning what the K
+        rows spanned; rank). The block is overwritten."""
+        T = _svqb_rotation(self.gram(block))
+        if T.shape[1] == 0:
+            return block[:0], 0
+        first = self.rotate(block, T)
+        T = _svqb_rotation(self.gram(first))
+        if T.shape[1] == 0:
+            return block[:0], 0
+        return self.rotate(first, T, block[:T.shape[1]]), T.shape[1]
 
 
 class _BlockPCG:

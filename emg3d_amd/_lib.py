@@ -14,7 +14,7 @@ LIBPATH = os.path.join(LIBDIR, 'libemg3d_amd.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'emg3d_amd.h')
 SOURCES = [os.path.join(CSRC, f) for f in ('kernels.hip', 'stencil.h', 'launch.h', 'cplx.h', 'receivers.h', 'krylov.h',
                                             'adjoint.h', 'reciprocal.h', 'hessian.h', 'hessian_blocks.h', 'gram.h',
-                                            'block.h', 'regularise.h', 'pcg_block.h', 'precondition.h')] + [HEADER]
+                                            'block.h', 'regularise.h', 'pcg_block.h', 'precondition.h', 'orthonormal.h')] + [HEADER]
 
 # -ffp-contract: hipcc's own default for HIP, spelled out because csrc/kernels.hip switches contraction off for its
 # line-kernel section and back to THIS mode behind it (`#pragma clang fp contract(fast)`: the pragma can name a mode,
@@ -158,6 +158,10 @@ SIGNATURES = {
     'emg3d_dev_data_space_filter': (_ci, [_ci, _ci, _ci] + [_vp] * 7 + [_sz, _vp]),
     'emg3d_dev_pcg_finish': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 5 + [_sz] + [_vp] * 4 + [_sz, _vp]),
     'emg3d_dev_pcg_direction_z': (_ci, [_sz, _ci, _ci, _ci] + [_vp] * 4),
+    # Gram matrix and rotation of a device block: the primitives of subspace methods
+    'emg3d_block_gram_ws_len': (_sz, [_sz, _ci]),
+    'emg3d_dev_block_gram': (_ci, [_sz, _ci, _vp, _sz, _vp, _vp, _vp]),
+    'emg3d_dev_block_rotate': (_ci, [_sz, _ci, _ci, _vp, _sz, _vp, _vp, _sz, _vp]),
     'emg3d_dev_source_field': (_ci, [_ci] * 4 + [_vp] * 7 + [_ci] + [ctypes.c_double] * 2 + [_vp] * 4),
     'emg3d_dev_volume_model': (_ci, [_ci] * 4 + [_vp] * 5 + [_ci] + [_vp] * 3 + [ctypes.c_double] * 4 + [_vp] * 5),
     'emg3d_dev_magnetic_field': (_ci, [_ci] * 4 + [_vp] * 7 + [ctypes.c_double] * 2 + [_vp] * 4),

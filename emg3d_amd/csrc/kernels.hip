@@ -2840,3 +2840,4 @@ int emg3d_core_solve(void *amat, void *bvec, int n, int is_complex)
 #include "regularise.h"
 #include "pcg_block.h"
 #include "precondition.h"
+#include "orthonormal.h"

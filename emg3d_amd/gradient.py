@@ -629,6 +629,14 @@ class ReciprocalSensitivity(Sensitivity):
     (block-Jacobi, ``emg3d_dev_pcg_update_blk`` / ``_direction_blk``).
     The outer inversion loop (line search, observed data, choice of the damping) is the user's.
 
+    The other consumer, after the step: ``sensitivity_svd``, a randomised truncated SVD ``W^1/2 J^ ~ U diag(s) V^T`` of the
+    weighted sensitivity from ``2 + 2 power_iterations`` half passes of the block products, whatever the number of data
+    is and on any computational grid -- a step from a truncated pseudo-inverse, the model resolution ``V V^T``, posterior
+    variances, the effective rank of a survey. Its two primitives serve any subspace method on device blocks:
+    ``orthonormalise_block`` makes the columns of a block orthonormal and reveals its rank (Gram-based SVQB applied
+    twice: ``emg3d_dev_block_gram``, ``eigh`` of the small matrix on the host, ``emg3d_dev_block_rotate``; DESIGN.md
+    4.21).
+
     field_dtype: ``'double'`` (default) keeps the fields as they are solved, ``n_edges x 16 B`` each. ``'single'``
         keeps them as complex64 (Laplace domain: float32): half the bytes in HBM or pinned memory, over PCIe with
         ``keep='host'``, and through the two HBM-bound products. Only the STORAGE is narrow: a solved
@@ -1140,6 +1148,113 @@ class ReciprocalSensitivity(Sensitivity):
         block = self._check_device_block(block, dev) if on_dev else self._upload_block(block, dev)
         out = self._gradient_block(self._pass(dev, len(block), kc, w).hessian_vec(block))
         return out if (on_dev if on_device is None else on_device) else self.from_device(out)
+
+    # ------------------------------------------------ orthonormal blocks and the truncated SVD ---
+    _MAX_BLOCK = 64          # columns of emg3d_dev_block_gram / emg3d_dev_block_rotate
+
+    def _check_block_columns(self, K, what):
+        if K > self._MAX_BLOCK:
+            raise ValueError(f"{what} must not exceed {self._MAX_BLOCK}, the widest block of `emg3d_dev_block_gram`. "
+                             f"Provided: {K}.")
+
+    def _orthonormaliser(self, dev, kmax):
+        from emg3d_amd._blockpass import _BlockOrth
+        return _BlockOrth(dev, kmax, _NCOMP[self.model.case] * self.model.grid.n_cells)
+
+    def orthonormalise_block(self, vectors, on_device=None):
+        """An orthonormal basis of the span of K <= 64 model vectors, in the Euclidean inner product of the vectors as
+        ``jtvec`` returns them: ``(Q, rank)``, ``Q`` with ``rank <= K`` columns -- fewer when the vectors are
+        numerically dependent. ``vectors`` and the form of ``Q`` as for ``hessian_vec_block``: a NumPy block gives
+        NumPy, a device block a device block (which is left as it is), ``on_device`` True / False decides otherwise; a
+        block of zeros gives ``rank`` 0 and an empty block of the same form, (0, n, n_cells) on the device.
+
+        Gram-based SVQB, applied twice: per application ``emg3d_dev_block_gram``, the K x K matrix on
+        the host (scaled to a unit diagonal, ``eigh``, directions below ``K eps`` times the largest eigenvalue dropped)
+        and ``emg3d_dev_block_rotate``. No Cholesky: a sketch of a sensitivity has a Gram matrix whose condition is the
+        square of an already fast decay. Scratch: one second block. Neither ``forward()`` nor the kept fields are
+        needed."""
+        on_dev, block = self._check_block(vectors)              # raises before any GPU work
+        self._check_block_columns(len(block), 'the number of `vectors`')
+        dev = self._device()
+        block = self._check_device_block(block, dev).clone() if on_dev else self._upload_block(block, dev).contiguous()
+        K, n, ncell = block.shape
+        q, rank = self._orthonormaliser(dev, K)(block.view(K, n * ncell))
+        to_dev = on_dev if on_device is None else on_device
+        if rank == 0:
+            return (block[:0] if to_dev else np.zeros((0,) + self._block_shapes()[2][0])), 0
+        q = q.view(rank, n, ncell)
+        return (q if to_dev else self.from_device(q)), rank
+
+    def sensitivity_svd(self, rank, weights=None, oversample=8, power_iterations=1, seed=0, on_device=False,
+                        columns_per_pass=8):
+        """Truncated singular value decomposition of the weighted sensitivity ``A = W^1/2 J^`` by the randomised range
+        finder of Halko, Martinsson and Tropp: ``A ~ U diag(s) V^T``. ``J^`` (M, N) has the rows ``Re J_i`` and ``Im J_i``
+        in the ordering of ``stack_data``, with the derivative chain of the mapping -- the matrix of ``data_gram`` --,
+        ``W`` the ``weights`` (as for ``hessian_diagonal``), repeated for the two rows of a datum.
+
+        Returns ``U`` (M, k) float64 with orthonormal columns, ``s`` (k,) descending, and ``V``: k model vectors shaped
+        like the result of ``jtvec``, NumPy (k,) + that shape or, ``on_device=True``, the device block (k, n, n_cells).
+        ``k <= rank``; it is smaller when the sketch is numerically rank-deficient (fewer data with a weight than
+        ``rank``). The entry of largest magnitude of every column of ``U`` (the first of them) is positive. It gives the
+        step of a truncated pseudo-inverse, the model resolution ``V V^T``, posterior variances, the effective rank of
+        a survey.
+
+        With ``l = min(rank + oversample, M)`` <= 64: ``Omega`` (M, l) standard normal from
+        ``numpy.random.default_rng(seed)`` on the host -- the result is a function of the arguments alone --, ``Y = J^T
+        W^1/2 Omega`` by the pass of ``jtvec_block``, ``Q = orth(Y)`` (``orthonormalise_block``), ``power_iterations``
+        times ``Q = orth(J^T W J Q)`` by the pass of ``hessian_vec_block``, ``B = W^1/2 J^ Q`` (M, l') by the pass of
+        ``jvec_block``, its thin SVD on the host, ``V = Q W_B`` by ``emg3d_dev_block_rotate``. ``2 +
+        2 power_iterations`` half passes over the kept fields whatever M is, through ONE pass object; nothing of
+        length N crosses the host but the final ``V`` with ``on_device=False``. Other computational grids (``grids=``)
+        are served as by the block products. Frequency-domain surveys only. No solve: ``n_solves`` does not move.
+
+        Accuracy: a power iteration works on the squares of the singular values, and its orthonormalisation drops what
+        falls below ``sqrt(l eps)`` of the largest. Singular values below about 1e-4 of ``s[0]`` come back less accurate
+        with ``power_iterations >= 1``, or not at all (``k`` smaller). Where the small end of the spectrum matters and
+        ``rank + oversample`` reaches M, ``power_iterations=0`` is exact to rounding."""
+        rank = self._check_count('rank', rank)                  # everything is validated before any GPU work
+        for name, value in (('oversample', oversample), ('power_iterations', power_iterations), ('seed', seed)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
+                raise ValueError(f"`{name}` must be an integer >= 0. Provided: {value!r}.")
+        w = self._check_weights(weights)
+        kc = self._check_columns(columns_per_pass)
+        if {float(f) < 0 for f in self.frequencies.values()} != {False}:
+            raise NotImplementedError("sensitivity_svd: frequency-domain surveys only; in the Laplace domain `jvec` is minus "
+                                      "the adjoint of `jtvec` (see `data_gram`): the passes do not form J^T W J there.")
+        nrec = len(self._rec[0])
+        M = 2 * len(self.pairs) * nrec
+        ell = min(rank + int(oversample), M)
+        self._check_block_columns(ell, 'min(`rank` + `oversample`, M)')
+        dev = self._device()
+        self.forward()
+        n, ncell = _NCOMP[self.model.case], self.model.grid.n_cells
+        root_w = np.tile(np.sqrt(np.concatenate([w[pair] for pair in self.pairs])), 2)
+        omega = np.random.default_rng(int(seed)).standard_normal((M, ell))
+        ps = self._pass(dev, ell, kc, w)
+        orth = self._orthonormaliser(dev, ell)
+
+        def orthonormal(grad):
+            q, r = orth(self._gradient_block(grad).view(len(grad), n * ncell))
+            if 0 < r < ps.K:
+                ps.shrink(r)
+            return q.view(r, n, ncell), r
+        q, r = orthonormal(ps.jtvec([self.unstack_data(root_w * omega[:, j]) for j in range(ell)]))
+        for _ in range(int(power_iterations)):
+            if r == 0:
+                break
+            q, r = orthonormal(ps.hessian_vec(q))
+        if r == 0:                                              # A = 0 to rounding: no datum carries a weight
+            return (np.zeros((M, 0)), np.zeros(0),
+                    q.view(0, n, ncell) if on_device else np.zeros((0,) + self._block_shapes()[2][0]))
+        jq = self._data_of(ps.jvec(q))
+        B = np.stack([root_w * self.stack_data({pair: jq[pair][j] for pair in jq}) for j in range(r)], axis=1)
+        U, s, Wt = np.linalg.svd(B, full_matrices=False)
+        k = min(rank, r)
+        U, s, Wb = np.ascontiguousarray(U[:, :k]), s[:k].copy(), Wt[:k].T
+        top = np.argmax(np.abs(U), axis=0)                      # (the first of equal magnitudes)
+        sign = np.where(U[top, np.arange(k)] < 0, -1.0, 1.0)
+        V = orth.rotate(q.view(r, n * ncell), Wb * sign[None, :]).view(k, n, ncell)
+        return U * sign[None, :], s, V.clone() if on_device else self.from_device(V)
 
     # ------------------------------------------- regulariser and the inner Gauss-Newton solve ---
     @staticmethod

@@ -747,6 +747,23 @@ int emg3d_dev_pcg_finish(size_t n_cells, int vec_per_col, int ncol, int first, d
                          void *stream);
 int emg3d_dev_pcg_direction_z(size_t n_cells, int vec_per_col, int ncol, int first, double *p, const double *z,
                               const double *table, void *stream);
+/* The two primitives of subspace methods on device blocks (randomised SVD, block Lanczos, Nystroem).
+ * A block is ncol rows of n doubles, `stride` doubles apart (the model blocks of the block products: n = components
+ * x cells). All fp64, no atomics, every sum in an order fixed by the sizes: same call, same bits. Nothing behind n
+ * is read in any row.
+ *
+ * emg3d_dev_block_gram: g[i * ncol + j] = sum_k y_i[k] y_j[k], ncol x ncol device doubles, symmetric bit for bit
+ * (i <= j is computed, [j, i] is its copy). Two stages: a partial per entry and chunk of 4096 elements into ws (at
+ * least emg3d_block_gram_ws_len(n, ncol) = ncol^2 ceil(n / 4096) doubles; 0 for sizes that are refused), then one
+ * workgroup per entry adds them (thread t of 256: t, t + 256, ..., then a binary tree).
+ * emg3d_dev_block_rotate: out_j[k] = sum_i y_i[k] t[i * ncol_out + j], the sum over i ascending; t: ncol_in x
+ * ncol_out device doubles, row-major. Out of place; nothing between the rows of out is written.
+ * EMG3D_ERR_BADARG, nothing launched: a NULL pointer, n < 1, ncol outside 1..64 (rotate: not 1 <= ncol_out <=
+ * ncol_in <= 64), a stride smaller than n, y and out overlapping. */
+size_t emg3d_block_gram_ws_len(size_t n, int ncol);
+int emg3d_dev_block_gram(size_t n, int ncol, const double *y, size_t stride, double *g, double *ws, void *stream);
+int emg3d_dev_block_rotate(size_t n, int ncol_in, int ncol_out, const double *y, size_t stride, const double *t,
+                           double *out, size_t out_stride, void *stream);
 
 /* ---- before a solve: model re-gridding -------------------------------
  * maps.interp_volume_average (emg3d/maps.py:555-616) behind Model.interpolate_to_grid

@@ -38,9 +38,13 @@ Leg ``blocks``: the cell blocks of the Hessian and block-Jacobi
 ``emg3d_dev_hessian_cell_blocks`` beside ``emg3d_dev_hessian_diagonal`` on the same inputs, taking turns (HIP events), an
 iteration of ``gauss_newton_solve`` with ``'block'`` beside ``True``, and iterations and wall time to ``tol = 1e-3`` of
 ``True``, ``'block'`` and ``'data'`` at the three dampings of the ``gndata`` leg. Writes profiles/hessian_blocks_times.txt.
+Leg ``svd``: the randomised truncated SVD: ``emg3d_dev_block_gram`` and ``emg3d_dev_block_rotate`` alone at
+8, 24 and 56 columns beside a copy of their bytes, an orthonormalisation beside the same steps from torch operations, and
+``sensitivity_svd`` at rank 16 and 48 beside ``data_gram`` + ``eigh`` + one ``jtvec_block``, taking turns. Writes
+profiles/sensitivity_svd_times.txt.
 
     python tools/sensitivity_time.py [--workload marine128] [--sources 4] [--repeat 3] [--launches 30]
-                                     [--leg all|products|hessian|gram|single|block|gnsolve|gndata|blocks]
+                                     [--leg all|products|hessian|gram|single|block|gnsolve|gndata|blocks|svd]
                                      [--field-dtype double|single]
                                      [--out profiles/sensitivity_times.txt]
                                      [--hessian-out profiles/hessian_diagonal_times.txt]
@@ -51,6 +55,7 @@ iteration of ``gauss_newton_solve`` with ``'block'`` beside ``True``, and iterat
                                      [--weighted-out profiles/weighted_regulariser_times.txt]
                                      [--gndata-out profiles/data_preconditioner_times.txt]
                                      [--blocks-out profiles/hessian_blocks_times.txt]
+                                     [--svd-out profiles/sensitivity_svd_times.txt]
 
 (COMMIT=<hash> in the environment names the commit on a box without git.)
 """
@@ -999,13 +1004,130 @@ def cell_blocks_block(rec, say, launches):
                 f"{info['preconditioner_passes']} passes, {t:.1f} ms with the set-up")
 
 
+SVD_COLS = (8, 24, 56)                   # columns of the kernels alone: l of rank 16 and 48 with oversample 8, and 8
+SVD_RANKS = (16, 48)
+
+
+def svd_block(rec, say, repeat, launches):
+    """The randomised SVD on the kept fields of ``rec``: ``emg3d_dev_block_gram`` and
+    ``emg3d_dev_block_rotate`` alone at ``SVD_COLS`` columns, each taking turns with a device copy of its bytes (HIP
+    events); an orthonormalisation of a block beside the same two SVQB steps written with torch operations (``Y @ Y.T``,
+    ``T.T.contiguous() @ Y``), taking turns; ``sensitivity_svd`` at ``SVD_RANKS`` beside the same factorisation by
+    ``data_gram`` + ``eigh`` + one ``jtvec_block``, taking turns, and how far their singular values are apart."""
+    from emg3d_amd import _lib
+    from emg3d_amd._blockpass import _BlockOrth, _svqb_rotation
+    from emg3d_amd._device import _ptr, _stream
+    L = _lib.lib()
+    grid = rec.model.grid
+    ncomp, ncell = gradient._NCOMP[rec.model.case], grid.n_cells
+    n = ncomp * ncell
+    dev = next(iter(rec._stacks.values()))[0].device
+    gen = torch.Generator(device=dev).manual_seed(0)
+    say(f"kernels alone: blocks of n = {ncomp} x {ncell:,} = {n:,} doubles per column, contiguous rows; medians of {launches} "
+        "launches (HIP events), every kernel taking turns with a device copy that moves its bytes")
+    for ncol in SVD_COLS:
+        Y = torch.randn((ncol, n), dtype=torch.float64, device=dev, generator=gen)
+        out = torch.empty_like(Y)
+        T = torch.randn((ncol, ncol), dtype=torch.float64, device=dev, generator=gen)
+        G = torch.empty(ncol * ncol, dtype=torch.float64, device=dev)
+        ws = torch.empty(L.emg3d_block_gram_ws_len(n, ncol), dtype=torch.float64, device=dev)
+
+        def k_gram():
+            _lib.check(L.emg3d_dev_block_gram(n, ncol, _ptr(Y), n, _ptr(G), _ptr(ws), _stream()), 'emg3d_dev_block_gram')
+
+        def k_rotate():
+            _lib.check(L.emg3d_dev_block_rotate(n, ncol, ncol, _ptr(Y), n, _ptr(T), _ptr(out), n, _stream()),
+                       'emg3d_dev_block_rotate')
+        half = Y[:max(ncol // 2, 1)]
+        what = [('block_gram', k_gram, 8 * ncol * n, lambda: out[:len(half)].copy_(half), 16 * len(half) * n),
+                ('block_rotate', k_rotate, 16 * ncol * n, lambda: out.copy_(Y), 16 * ncol * n)]
+        for name, fn, nbytes, copy, cbytes in what:
+            ms = {'kernel': [], 'copy': []}
+            for r in range(launches + 3):                # three warm-up rounds; the two take turns
+                for key, f in (('kernel', fn), ('copy', copy)):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    f()
+                    b.record()
+                    b.synchronize()
+                    if r >= 3:
+                        ms[key].append(a.elapsed_time(b))
+            q, c = np.percentile(ms['kernel'], [50, 25, 75]), np.percentile(ms['copy'], [50, 25, 75])
+            flops = (ncol * (ncol + 1) if name == 'block_gram' else 2 * ncol * ncol) * n
+            say(f"  {name:12s} ncol {ncol:2d}: median {q[0]:8.4f} ms (quartiles {q[1]:.4f} .. {q[2]:.4f}) = "
+                f"{nbytes / q[0] / 1e9:6.3f} TB/s on {nbytes:,} algorithmic B, {flops / q[0] / 1e9:6.2f} TFLOP/s fp64; copy of "
+                f"{cbytes:,} B (read + written): {c[0]:8.4f} ms (quartiles {c[1]:.4f} .. {c[2]:.4f}) = {cbytes / c[0] / 1e9:6.3f} "
+                f"TB/s; kernel / copy {q[0] / c[0]:.2f}")
+        del Y, out, T, G, ws, half, what
+    say(f"orthonormalisation of a block (two SVQB steps; wall, synchronised, download of G, eigh on the host and upload of T "
+        f"included), the library's kernels beside torch operations (Y @ Y.T, T.T.contiguous() @ Y), taking turns, {repeat} rounds after a warm-up:")
+    for ncol in SVD_COLS:
+        Y0 = torch.randn((ncol, n), dtype=torch.float64, device=dev, generator=gen)
+        orth = _BlockOrth(dev, ncol, n)
+
+        def by_library():
+            return orth(Y0.clone())[0]
+
+        def by_torch():
+            Q = Y0
+            for _ in range(2):
+                T = torch.from_numpy(_svqb_rotation((Q @ Q.T).cpu().numpy())).to(dev)
+                Q = T.T.contiguous() @ Q
+            return Q
+        per = {'library': [], 'torch': []}
+        for r in range(repeat + 1):
+            for key, f in (('library', by_library), ('torch', by_torch)):
+                t, Q = wall(f)
+                if r:
+                    per[key].append(t)
+        err = {key: float((f() @ f().T - torch.eye(ncol, dtype=torch.float64, device=dev)).abs().max())
+               for key, f in (('library', by_library), ('torch', by_torch))}
+        say(f"  ncol {ncol:2d}: library {' '.join(f'{t:.3f}' for t in per['library'])} ms (mean {np.mean(per['library']):.3f}); torch "
+            f"{' '.join(f'{t:.3f}' for t in per['torch'])} ms (mean {np.mean(per['torch']):.3f}); ratio of the means torch / library "
+            f"{np.mean(per['torch']) / np.mean(per['library']):.2f}; max |Q Q^T - I|: library {err['library']:.1e}, torch "
+            f"{err['torch']:.1e}")
+        del Y0, orth
+    M = 2 * len(rec.pairs) * len(rec._rec[0])
+    say(f"sensitivity_svd(rank, oversample=8, power_iterations=1, on_device=True), all weights one, M = {M}, beside data_gram + "
+        f"eigh + one jtvec_block of `rank` columns (V = J^T U / s, on the device); wall, synchronised, taking turns, {repeat} "
+        "rounds after a warm-up:")
+    for rank in SVD_RANKS:
+        def by_sketch():
+            return rec.sensitivity_svd(rank, oversample=8, power_iterations=1, on_device=True)
+
+        def by_gram():
+            lam, Z = np.linalg.eigh(rec.data_gram())
+            lam, Z = lam[::-1][:rank], Z[:, ::-1][:, :rank]
+            s = np.sqrt(np.maximum(lam, 0.0))
+            return Z, s, rec.jtvec_block([rec.unstack_data(Z[:, j] / s[j]) for j in range(rank)], on_device=True)
+        per = {'sketch': [], 'gram': []}
+        for r in range(repeat + 1):
+            for key, f in (('sketch', by_sketch), ('gram', by_gram)):
+                t, res = wall(f)
+                if r:
+                    per[key].append(t)
+                if key == 'sketch':
+                    s_sketch = res[1]
+                else:
+                    s_gram = res[1]
+                del res
+        k = min(len(s_sketch), len(s_gram))
+        rel = np.abs(s_sketch[:k] - s_gram[:k]) / s_gram[0]
+        say(f"  rank {rank:2d} (l = {min(rank + 8, M)}): sensitivity_svd {' '.join(f'{t:.2f}' for t in per['sketch'])} ms (mean "
+            f"{np.mean(per['sketch']):.2f}); data_gram route {' '.join(f'{t:.2f}' for t in per['gram'])} ms (mean "
+            f"{np.mean(per['gram']):.2f}); ratio of the means gram / sketch {np.mean(per['gram']) / np.mean(per['sketch']):.2f}; k = "
+            f"{len(s_sketch)}, s_1 = {s_gram[0]:.3e}, s_k / s_1 = {s_gram[k - 1] / s_gram[0]:.2e}, max |s - s_gram| / s_1 = "
+            f"{float(np.max(rel)):.2e} (largest at j = {int(np.argmax(rel)) + 1})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='marine128')
     ap.add_argument('--sources', type=int, default=4)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--launches', type=int, default=30, help="timed launches per kernel of the kernel block (>= 20)")
-    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block', 'gnsolve', 'gndata', 'blocks'),
+    ap.add_argument('--leg', choices=('all', 'products', 'hessian', 'gram', 'single', 'block', 'gnsolve', 'gndata', 'blocks',
+                                     'svd'),
                     default='all',
                     help="products: the inner iteration four ways and its two reductions; hessian: hessian_diagonal against "
                          "the row-by-row route (needs only the set-up of ReciprocalSensitivity); gram: data_gram against the "
@@ -1015,7 +1137,9 @@ def main():
                          "iteration of gauss_newton_solve, its kernels and the same iteration from torch operations (not "
                          "part of 'all'); gndata: the data-space preconditioner of gauss_newton_solve beside Jacobi (not part "
                          "of 'all'); blocks: the cell blocks of the Hessian beside its diagonal and block-Jacobi beside Jacobi "
-                         "and the data-space preconditioner (not part of 'all')")
+                         "and the data-space preconditioner (not part of 'all'); svd: the kernels of the randomised SVD, the "
+                         "orthonormalisation beside torch operations and sensitivity_svd beside the data_gram route (not part of "
+                         "'all')")
     ap.add_argument('--field-dtype', choices=('double', 'single'), default='double',
                     help="how ReciprocalSensitivity keeps its fields in the reciprocal, hessian and gram legs")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sensitivity_times.txt'))
@@ -1027,6 +1151,7 @@ def main():
     ap.add_argument('--weighted-out', default=os.path.join(ROOT, 'profiles', 'weighted_regulariser_times.txt'))
     ap.add_argument('--gndata-out', default=os.path.join(ROOT, 'profiles', 'data_preconditioner_times.txt'))
     ap.add_argument('--blocks-out', default=os.path.join(ROOT, 'profiles', 'hessian_blocks_times.txt'))
+    ap.add_argument('--svd-out', default=os.path.join(ROOT, 'profiles', 'sensitivity_svd_times.txt'))
     args = ap.parse_args()
     K = args.sources
     wl = workload(args.workload)
@@ -1171,6 +1296,19 @@ def main():
         rec.release()
         os.makedirs(os.path.dirname(os.path.abspath(args.blocks_out)), exist_ok=True)
         with open(args.blocks_out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
+    if args.leg == 'svd':
+        lines[1] = (f"# {wl['label']}; {K} sources x 1 frequency, {len(recs)} receivers; the randomised truncated SVD of the "
+                    "sensitivity, all weights one, field_dtype 'double'; times in ms")
+        rec = gradient.ReciprocalSensitivity(model, sources, freqs, recs, solver_opts=dict(wl['opts'], tol=1e-6), keep='device',
+                                             batch=K)
+        rec.forward()
+        say(f"{rec!r}")
+        svd_block(rec, say, args.repeat, args.launches)
+        rec.release()
+        os.makedirs(os.path.dirname(os.path.abspath(args.svd_out)), exist_ok=True)
+        with open(args.svd_out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
         return
     if args.leg in ('hessian', 'gram'):
